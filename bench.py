@@ -13,7 +13,13 @@ polishes a full C. elegans-sized 100 Mbp genome per step at 30x coverage).
 A step is the whole job: parse, align overlaps, route windows, POA
 consensus on the GPU, and gather of the polished contigs to rank 0.
 
-Usage: python bench.py --gpus N --steps K --warmup W
+Usage: python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints one JSON result
+line; that is all the headline figure needs. --dump-outputs DIR additionally
+writes what the last timed step returned (see dump_outputs). --full is the
+switch for any secondary measurement (baselines, other configurations); the
+benchmark has none today, so it currently runs the same work as a plain run.
 """
 
 import argparse
@@ -39,6 +45,43 @@ def log(msg):
     print(msg, file=sys.stderr, flush=True)
 
 
+# --dump-outputs budget: 64 MB in all; the float32 consensus array gets
+# 15 Mi elements (60 MB), the rest is headroom for lengths and headers.
+DUMP_MAX_ELEMS = 15 * 1024 * 1024
+DUMP_SEED = 20240229
+
+
+def dump_outputs(outdir, seqs):
+    """Writes the polished contigs a caller of the timed path receives.
+
+    seqs: polished sequences in output order (on a multi-rank run, rank 0's
+    gathered per-rank consensus blobs). Files:
+      contig_lengths.npy  float64, length of every sequence
+      consensus.npy       float32, ASCII codes of the concatenated sequences;
+                          beyond DUMP_MAX_ELEMS a fixed seeded sample of
+                          positions (ascending) is kept instead
+      consensus_index.npy float64, the sampled positions (only when sampled)
+    """
+    import numpy as np
+
+    outdir = Path(outdir)
+    outdir.mkdir(parents=True, exist_ok=True)
+    lengths = np.array([len(s) for s in seqs], dtype=np.float64)
+    codes = np.frombuffer(b"".join(seqs), dtype=np.uint8)
+    index_path = outdir / "consensus_index.npy"
+    if codes.size > DUMP_MAX_ELEMS:
+        rng = np.random.default_rng(DUMP_SEED)
+        # a sample costs 12 bytes: float32 value + float64 position
+        n = DUMP_MAX_ELEMS // 3
+        idx = np.sort(rng.choice(codes.size, size=n, replace=False))
+        codes = codes[idx]
+        np.save(index_path, idx.astype(np.float64))
+    elif index_path.exists():
+        index_path.unlink()
+    np.save(outdir / "contig_lengths.npy", lengths)
+    np.save(outdir / "consensus.npy", codes.astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -55,6 +98,10 @@ def main():
     ap.add_argument("--banded", action="store_true",
                     help="use -b static-band POA (approximation; off by default)")
     ap.add_argument("--cpu", action="store_true", help="force CPU path (debug)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's polished contigs as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run secondary measurements (none exist today)")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", 1))
@@ -109,12 +156,14 @@ def main():
                             banded_poa=args.banded)
         # gather polished contigs to rank 0: length-prefixed point-to-point
         # over RCCL/xGMI (comm.cpp) — each rank's exact bytes, no padding
+        received = out
         if world > 1:
             blob = "".join(s for _, s in out).encode()
             parts = _racon.comm_gather(blob, 0)
             if rank == 0:
                 assert len(parts) == world
-        return sum(len(s) for _, s in out)
+            received = parts
+        return sum(len(s) for _, s in out), received
 
     def barrier_sync():
         # barrier + full device sync on both sides of the timed region
@@ -131,8 +180,10 @@ def main():
     barrier_sync()
     t0 = time.perf_counter()
     polished_bp = 0
+    received = []
     for _ in range(args.steps):
-        polished_bp += one_step()
+        step_bp, received = one_step()
+        polished_bp += step_bp
     barrier_sync()
     elapsed = time.perf_counter() - t0
 
@@ -140,6 +191,13 @@ def main():
     if world > 1:
         elapsed = _racon.comm_allreduce_max(elapsed)
         polished_bp = _racon.comm_allreduce_sum(float(polished_bp))
+
+    if rank == 0 and args.dump_outputs:
+        if world > 1:
+            seqs = [bytes(p) for p in received]
+        else:
+            seqs = [s.encode() for _, s in received]
+        dump_outputs(args.dump_outputs, seqs)
 
     if rank == 0:
         value = polished_bp / 1e6 / elapsed

@@ -14,10 +14,10 @@ PY
 echo "asan OK"
 
 # deeper pass: the reference golden workload end-to-end under ASan
-if [ -d /root/reference/test/data ]; then
-  ./build-asan/racon -t 8 -m 5 -x -4 -g -8 \
-      /root/reference/test/data/sample_reads.fastq.gz \
-      /root/reference/test/data/sample_overlaps.paf.gz \
-      /root/reference/test/data/sample_layout.fasta.gz > /dev/null
-  echo "asan golden OK"
-fi
+GOLDEN=tests/golden/lambda
+cat $GOLDEN/sample_reads.fastq.gz.part* > build-asan/sample_reads.fastq.gz
+./build-asan/racon -t 8 -m 5 -x -4 -g -8 \
+    build-asan/sample_reads.fastq.gz \
+    $GOLDEN/sample_overlaps.paf.gz \
+    $GOLDEN/sample_layout.fasta.gz > /dev/null
+echo "asan golden OK"

@@ -1,17 +1,33 @@
 #!/usr/bin/env python3
-"""Quick golden comparison harness against the reference sample data.
+"""Quick golden comparison harness against the reference sample data
+(tests/golden/lambda).
 
 Usage: python3 tests/golden_check.py [builddir]
 Prints one line per scenario: <golden> <ours> <delta>.
 """
 import sys
 import gzip
+import tempfile
+from pathlib import Path
 
 BUILD = sys.argv[1] if len(sys.argv) > 1 else "build"
 sys.path.insert(0, BUILD)
 import _racon  # noqa: E402
 
-D = "/root/reference/test/data/"
+GOLDEN = Path(__file__).resolve().parent / "golden" / "lambda"
+
+
+def stage_sample():
+    """Copies the sample into a temp dir, joining the byte-split fastq."""
+    d = Path(tempfile.mkdtemp(prefix="racon_golden_"))
+    for f in sorted(GOLDEN.iterdir()):
+        stem = f.name.partition(".part")[0]
+        with open(d / stem, "ab") as out:
+            out.write(f.read_bytes())
+    return str(d) + "/"
+
+
+D = stage_sample()
 
 
 def read_fasta(path):
