@@ -37,6 +37,7 @@ class Graph {
   Graph() = default;
 
   const std::vector<Node>& nodes() const { return nodes_; }
+  uint32_t num_nodes() const { return static_cast<uint32_t>(nodes_.size()); }
   const std::vector<Edge>& edges() const { return edges_; }
   const std::vector<uint32_t>& sorted_node_ids() const { return sorted_; }
 

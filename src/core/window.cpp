@@ -135,6 +135,7 @@ bool Window::generate_consensus(poa::NWEngine& engine, bool trim) {
 
   std::vector<uint32_t> coverages;
   consensus_ = graph.generate_consensus(&coverages);
+  graph_nodes_ = graph.num_nodes();
 
   if (type_ == WindowType::kTGS && trim) {
     const uint32_t cov_floor = static_cast<uint32_t>(layers_.size() - 1) / 2;

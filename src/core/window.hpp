@@ -76,12 +76,17 @@ class Window {
   // (false = backbone copy for under-covered windows).
   bool generate_consensus(poa::NWEngine& engine, bool trim);
 
+  // Node count of the POA graph after the last generate_consensus() (0 when
+  // no graph was built); the GPU engine's node caps are tested against it.
+  uint32_t graph_nodes() const { return graph_nodes_; }
+
  private:
   uint64_t contig_id_;
   uint32_t rank_;
   WindowType type_;
   std::string consensus_;
   std::vector<Layer> layers_;
+  uint32_t graph_nodes_ = 0;
 };
 
 std::shared_ptr<Window> createWindow(uint64_t id, uint32_t rank, WindowType type,

@@ -35,8 +35,12 @@ class AlignerBatch {
                    bool* never_fits);
 
   // Raw-span variant (testing / direct use): returns the slot index, -1 when
-  // the batch is full, -2 when the pair can never run here.
-  int32_t reserve_span(const char* q, uint32_t q_len, const char* t, uint32_t t_len);
+  // the batch is full, -2 when the pair can never run here: empty or over-long
+  // sequences, or non-ACGT bytes in both of them (checked unless
+  // scan_non_acgt is false, for callers that already know one side is pure
+  // A/C/G/T).
+  int32_t reserve_span(const char* q, uint32_t q_len, const char* t, uint32_t t_len,
+                       bool scan_non_acgt = true);
 
   // Runs the kernel over everything reserved (pack + sub-launches + D2H).
   void run();

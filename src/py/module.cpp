@@ -147,6 +147,39 @@ std::vector<std::pair<std::string, bool>> poa_windows_cpu(
   return out;
 }
 
+// CPU-only: node count of each window's CPU POA graph after all layers
+// (0 for under-covered windows, which build no graph). Lets tests construct
+// windows that provably exceed the GPU engine's node caps.
+std::vector<uint32_t> poa_window_node_counts(
+    const std::vector<std::vector<std::tuple<std::string, std::string, uint32_t, uint32_t>>>&
+        window_layers,
+    int8_t match, int8_t mismatch, int8_t gap) {
+  py::gil_scoped_release release;
+  rga::poa::NWEngine engine(match, mismatch, gap);
+  std::vector<uint32_t> out;
+  out.reserve(window_layers.size());
+  for (const auto& layers : window_layers) {
+    if (layers.empty()) {
+      throw std::runtime_error("poa_window_node_counts: window without a backbone");
+    }
+    const auto& bb = layers.front();
+    auto w = rga::createWindow(0, 0, rga::WindowType::kTGS, std::get<0>(bb).data(),
+                               static_cast<uint32_t>(std::get<0>(bb).size()),
+                               std::get<1>(bb).data(),
+                               static_cast<uint32_t>(std::get<1>(bb).size()));
+    for (size_t i = 1; i < layers.size(); ++i) {
+      const auto& l = layers[i];
+      const std::string& q = std::get<1>(l);
+      w->add_layer(std::get<0>(l).data(), static_cast<uint32_t>(std::get<0>(l).size()),
+                   q.empty() ? nullptr : q.data(), static_cast<uint32_t>(q.size()),
+                   std::get<2>(l), std::get<3>(l));
+    }
+    w->generate_consensus(engine, false);
+    out.push_back(w->graph_nodes());
+  }
+  return out;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(_racon, m) {
@@ -215,6 +248,8 @@ PYBIND11_MODULE(_racon, m) {
   m.def("poa_windows_cpu", &poa_windows_cpu, py::arg("windows"), py::arg("match") = 3,
         py::arg("mismatch") = -5, py::arg("gap") = -4, py::arg("trim") = true,
         py::arg("tgs") = true);
+  m.def("poa_window_node_counts", &poa_window_node_counts, py::arg("windows"),
+        py::arg("match") = 3, py::arg("mismatch") = -5, py::arg("gap") = -4);
   m.def("poa_windows_gpu", [](const std::vector<std::vector<
                                   std::tuple<std::string, std::string, uint32_t, uint32_t>>>& w,
                               int8_t match, int8_t mismatch, int8_t gap, bool banded,
