@@ -6,6 +6,7 @@
 #include <chrono>
 #include <cstring>
 #include <stdexcept>
+#include <type_traits>
 
 #include "hip/hip_common.hpp"
 
@@ -15,21 +16,7 @@ namespace {
 
 constexpr size_t kSeqArenaPerWindow = 96 * 1024;  // bases+weights staging per window (avg)
 
-size_t slab_bytes(const PoaLimits& L) {
-  size_t n = L.max_nodes;
-  size_t b = 0;
-  b += 4 * n;                       // letters, in_cnt, out_cnt, ring_cnt
-  b += n * L.max_edges * 8;         // in_edges(2) + in_weights(4) + out_edges(2)
-  b += n * L.max_ring * 2;          // ring
-  b += n * 2 * 2;                   // nseq, rank
-  b += n * 12;                      // hb_score(8) + hb_pred(4)
-  b += (2 * L.matrix_width + n) * 8;  // aln_nodes + aln_seq
-  b += (n + 1) * L.matrix_width * 2;  // matrix
-  b += (n + 1) * L.matrix_width;      // moves
-  b += n * 8;                         // row_desc
-  b += 64;                            // timing
-  return b;
-}
+constexpr PoaLimits L = kPoaLimits;
 
 }  // namespace
 
@@ -38,7 +25,7 @@ PoaBatch::PoaBatch(int device, size_t mem_budget, int8_t match, int8_t mismatch,
     : device_(device), match_(match), mismatch_(mismatch), gap_(gap), max_depth_(max_depth) {
   // int16 score guard: worst |score| <= (max_nodes + matrix_width) * max|param|
   // (banded mode additionally reserves values below -28000 as out-of-band)
-  int32_t worst = static_cast<int32_t>(limits_.max_nodes + limits_.matrix_width) *
+  int32_t worst = static_cast<int32_t>(L.max_nodes + L.matrix_width) *
                   std::max({std::abs(static_cast<int32_t>(match)),
                             std::abs(static_cast<int32_t>(mismatch)),
                             std::abs(static_cast<int32_t>(gap))});
@@ -50,25 +37,8 @@ PoaBatch::PoaBatch(int device, size_t mem_budget, int8_t match, int8_t mismatch,
     snprintf(msg, sizeof(msg),
              "[rga::hip::PoaBatch] score parameters too large for int16 GPU "
              "scores (|m|,|x|,|g| must keep (%u+%u)*max <= %d)",
-             limits_.max_nodes, limits_.matrix_width, banded ? 27000 : 28000);
+             L.max_nodes, L.matrix_width, banded ? 27000 : 28000);
     throw std::runtime_error(msg);
-  }
-
-  // The kernel compiles the capacity model as constants (poa_kernel.hip
-  // keeps slab addressing in immediates); this object must not deviate
-  // from the PoaLimits defaults without recompiling the kernel.
-  {
-    PoaLimits defaults;
-    if (limits_.max_seq_len != defaults.max_seq_len ||
-        limits_.max_nodes != defaults.max_nodes ||
-        limits_.max_edges != defaults.max_edges ||
-        limits_.max_ring != defaults.max_ring ||
-        limits_.matrix_width != defaults.matrix_width ||
-        limits_.max_consensus != defaults.max_consensus) {
-      throw std::runtime_error(
-          "[rga::hip::PoaBatch] PoaLimits diverged from the compile-time "
-          "kernel capacity model");
-    }
   }
 
   RGA_HIP_TRY(hipSetDevice(device_));
@@ -76,9 +46,9 @@ PoaBatch::PoaBatch(int device, size_t mem_budget, int8_t match, int8_t mismatch,
   RGA_HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
   stream_ = s;
 
-  const size_t per_window = slab_bytes(limits_) + kSeqArenaPerWindow +
-                            limits_.max_consensus * 3 + sizeof(PoaWindowDesc) + 1024;
-  // slab cap: 4096 default; RGA_POA_SLABS raises it for single-mega-batch
+  const size_t per_window = poa_slab_bytes() + kSeqArenaPerWindow +
+                            L.max_consensus * 3 + sizeof(PoaWindowDesc) + 1024;
+  // slab cap: 8192 default; RGA_POA_SLABS raises it for single-mega-batch
   // experiments (all windows in one launch vs several contending launches)
   static const size_t slab_cap = [] {
     const char* e = getenv("RGA_POA_SLABS");
@@ -104,55 +74,37 @@ PoaBatch::PoaBatch(int device, size_t mem_budget, int8_t match, int8_t mismatch,
 // setups (rehearsals, several ranks per GPU) must degrade to smaller
 // batches, not die (the round-1 sizing assumed one exclusive device).
 void PoaBatch::allocate_arenas(bool banded) {
-  const PoaLimits& L = limits_;
-  const size_t n = L.max_nodes;
-  size_t total = 0;
-  auto carve = [&total](size_t bytes) {
-    size_t off = total;
-    total += (bytes + 255) & ~size_t(255);
-    return off;
-  };
+  // Lays every array out from `base` in allocation order, each rounded up
+  // to 256 bytes, pointing arena_ at them; returns the pool size. Run with a
+  // null base to size the pool, then again with the allocation.
   size_t max_layers = 0;
-  size_t o_spans = 0;
-  size_t o_seq = 0, o_wt = 0, o_ends = 0, o_ends_idx = 0, o_desc = 0, o_letters = 0,
-         o_in_cnt = 0, o_out_cnt = 0, o_ring_cnt = 0, o_in_edges = 0, o_in_w = 0,
-         o_out_edges = 0, o_ring = 0, o_nseq = 0, o_rank = 0, o_hb_score = 0, o_hb_pred = 0,
-         o_aln_n = 0, o_aln_s = 0, o_matrix = 0, o_moves = 0, o_rd = 0, o_timing = 0,
-         o_cons = 0, o_cov = 0, o_clen = 0, o_status = 0;
+  auto lay_out = [&](void* base) {
+    size_t total = 0;
+    auto carve = [&](auto*& p, size_t count) {
+      p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(
+          reinterpret_cast<uintptr_t>(base) + total);
+      total += (count * sizeof(*p) + 255) & ~size_t(255);
+    };
+    const size_t slabs = num_slabs_;
+    carve(arena_.seq_data, seq_arena_cap_);
+    carve(arena_.weight_data, seq_arena_cap_);
+    carve(arena_.layer_ends, max_layers);
+    carve(arena_.layer_spans, max_layers);
+    carve(arena_.layer_ends_index, slabs + 1);
+    carve(arena_.windows, slabs);
+    for_each_poa_slab(arena_.slabs,
+                      [&](auto*& p, size_t count) { carve(p, slabs * count); });
+    carve(arena_.timing, slabs * kPoaTimingSlots);
+    carve(arena_.consensus, slabs * L.max_consensus);
+    carve(arena_.coverage, slabs * L.max_consensus);
+    carve(arena_.consensus_len, slabs);
+    carve(arena_.status, slabs);
+    return total;
+  };
   for (;; num_slabs_ /= 2) {
     seq_arena_cap_ = static_cast<size_t>(num_slabs_) * kSeqArenaPerWindow;
     max_layers = static_cast<size_t>(num_slabs_) * (max_depth_ + 1);
-    total = 0;
-    o_seq = carve(seq_arena_cap_);
-    o_wt = carve(seq_arena_cap_);
-    o_ends = carve(max_layers * 4);
-    o_spans = carve(max_layers * 4);
-    o_ends_idx = carve((num_slabs_ + 1) * 4);
-    o_desc = carve(num_slabs_ * sizeof(PoaWindowDesc));
-    o_letters = carve(num_slabs_ * n);
-    o_in_cnt = carve(num_slabs_ * n);
-    o_out_cnt = carve(num_slabs_ * n);
-    o_ring_cnt = carve(num_slabs_ * n);
-    o_in_edges = carve(num_slabs_ * n * L.max_edges * 2);
-    o_in_w = carve(num_slabs_ * n * L.max_edges * 4);
-    o_out_edges = carve(num_slabs_ * n * L.max_edges * 2);
-    o_ring = carve(num_slabs_ * n * L.max_ring * 2);
-    o_nseq = carve(num_slabs_ * n * 2);
-    o_rank = carve(num_slabs_ * n * 2);
-    o_hb_score = carve(num_slabs_ * n * 8);
-    o_hb_pred = carve(num_slabs_ * n * 4);
-    o_aln_n = carve(num_slabs_ * (2 * L.matrix_width + n) * 4);
-    o_aln_s = carve(num_slabs_ * (2 * L.matrix_width + n) * 4);
-    o_matrix = carve(num_slabs_ * (n + 1) * L.matrix_width * 2);
-    o_moves = carve(num_slabs_ * (n + 1) * L.matrix_width);
-    o_rd = carve(num_slabs_ * n * 8);
-    o_timing = carve(static_cast<size_t>(num_slabs_) * 8 * 8);
-    o_cons = carve(static_cast<size_t>(num_slabs_) * L.max_consensus);
-    o_cov = carve(static_cast<size_t>(num_slabs_) * L.max_consensus * 2);
-    o_clen = carve(num_slabs_ * 4);
-    o_status = carve(num_slabs_ * 4);
-
-    hipError_t err = hipMalloc(&d_pool_, total);
+    hipError_t err = hipMalloc(&d_pool_, lay_out(nullptr));
     if (err == hipSuccess) {
       break;
     }
@@ -173,50 +125,17 @@ void PoaBatch::allocate_arenas(bool banded) {
   RGA_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h_desc_),
                             num_slabs_ * sizeof(PoaWindowDesc)));
   RGA_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h_consensus_),
-                            static_cast<size_t>(num_slabs_) * limits_.max_consensus));
+                            static_cast<size_t>(num_slabs_) * L.max_consensus));
   RGA_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h_coverage_),
-                            static_cast<size_t>(num_slabs_) * limits_.max_consensus * 2));
+                            static_cast<size_t>(num_slabs_) * L.max_consensus * 2));
   RGA_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h_consensus_len_), num_slabs_ * 4));
   RGA_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h_status_), num_slabs_ * 4));
 
-  auto base = static_cast<uint8_t*>(d_pool_);
-  arena_.seq_data = base + o_seq;
-  arena_.weight_data = base + o_wt;
-  arena_.layer_ends = reinterpret_cast<uint32_t*>(base + o_ends);
-  arena_.layer_spans = reinterpret_cast<uint32_t*>(base + o_spans);
-  arena_.layer_ends_index = reinterpret_cast<uint32_t*>(base + o_ends_idx);
-  arena_.windows = reinterpret_cast<PoaWindowDesc*>(base + o_desc);
-  arena_.letters = base + o_letters;
-  arena_.in_cnt = base + o_in_cnt;
-  arena_.out_cnt = base + o_out_cnt;
-  arena_.ring_cnt = base + o_ring_cnt;
-  arena_.in_edges = reinterpret_cast<uint16_t*>(base + o_in_edges);
-  arena_.in_weights = reinterpret_cast<int32_t*>(base + o_in_w);
-  arena_.out_edges = reinterpret_cast<uint16_t*>(base + o_out_edges);
-  arena_.ring = reinterpret_cast<uint16_t*>(base + o_ring);
-  arena_.nseq = reinterpret_cast<uint16_t*>(base + o_nseq);
-  arena_.rank = reinterpret_cast<uint16_t*>(base + o_rank);
-  arena_.hb_score = reinterpret_cast<int64_t*>(base + o_hb_score);
-  arena_.hb_pred = reinterpret_cast<int32_t*>(base + o_hb_pred);
-  arena_.aln_nodes = reinterpret_cast<int32_t*>(base + o_aln_n);
-  arena_.aln_seq = reinterpret_cast<int32_t*>(base + o_aln_s);
-  arena_.matrix = reinterpret_cast<int16_t*>(base + o_matrix);
-  arena_.moves = base + o_moves;
-  arena_.row_desc = reinterpret_cast<uint64_t*>(base + o_rd);
-  arena_.timing = reinterpret_cast<unsigned long long*>(base + o_timing);
-  arena_.consensus = base + o_cons;
-  arena_.coverage = reinterpret_cast<uint16_t*>(base + o_cov);
-  arena_.consensus_len = reinterpret_cast<uint32_t*>(base + o_clen);
-  arena_.status = reinterpret_cast<int32_t*>(base + o_status);
-  arena_.vstore_mode = [] {
-    const char* e = getenv("RGA_VSTORE");
-    return e != nullptr ? static_cast<uint32_t>(atoi(e)) : 1u;
-  }();
+  lay_out(d_pool_);
   arena_.match = match_;
   arena_.mismatch = mismatch_;
   arena_.gap = gap_;
   arena_.band_width = banded ? 256 : 0;  // reference static band 256
-  arena_.limits = limits_;
 }
 
 PoaBatch::~PoaBatch() { release_all(); }
@@ -246,7 +165,7 @@ bool PoaBatch::add_window(const std::shared_ptr<Window>& window, bool* never_fit
   const uint32_t total_layers = window->num_layers();
 
   // backbone must fit the DP row; otherwise this window can never run here
-  if (window->sequence(0).second + 1 > limits_.matrix_width) {
+  if (window->sequence(0).second + 1 > L.matrix_width) {
     *never_fits = true;
     return false;
   }
@@ -264,7 +183,7 @@ bool PoaBatch::add_window(const std::shared_ptr<Window>& window, bool* never_fit
   for (uint32_t k = 1; k < total_layers && shipped < max_depth_ + 1; ++k) {
     uint32_t i = order[k];
     uint32_t len = window->sequence(i).second;
-    if (len + 1 > limits_.matrix_width) {
+    if (len + 1 > L.matrix_width) {
       continue;  // reference: exceeded_maximum_sequence_size -> skipped
     }
     bytes += len;
@@ -312,7 +231,7 @@ void PoaBatch::pack() {
       uint32_t i = order[k];
       auto seq = window->sequence(i);
       auto qual = window->quality(i);
-      if (k > 0 && seq.second + 1 > limits_.matrix_width) {
+      if (k > 0 && seq.second + 1 > L.matrix_width) {
         continue;
       }
       uint32_t span_word = 0xFFFFFFFFu;  // backbone / spanning layers: full DP
@@ -352,50 +271,26 @@ std::vector<bool> PoaBatch::generate(bool trim) {
 
   pack();
   const size_t nw0 = windows_.size();
-  // order: columns-per-lane bucket first (each bucket is its own kernel
-  // instantiation launched over a contiguous desc range), heaviest windows
-  // first within a bucket (blocks launch roughly in order, so the long
-  // poles start early instead of defining the tail)
+  // order: kernel variant first (each is its own instantiation launched
+  // over a contiguous desc range), heaviest windows first within a variant
+  // (blocks launch roughly in order, so the long poles start early instead
+  // of defining the tail)
   std::vector<uint32_t> perm(nw0);
   for (uint32_t i = 0; i < nw0; ++i) perm[i] = i;
-  auto bucket = [&](uint32_t w) -> uint32_t {
-    // (wb, ring-width) variants — see launch_poa_kernel. The LDS ring is
-    // indexed by ABSOLUTE column, so its width follows the true longest
-    // row (aw); only the columns-per-pass choice (WB) follows the banded
-    // clamp. 9-wide single-pass was tried and spills 44-64 B/lane of
-    // scratch, which is catastrophically slow; 8-wide multi-pass covers
-    // any width, and the ring width picks the smallest LDS footprint the
-    // rows fit in.
-    const uint32_t aw = h_desc_[w].max_len;
-    uint32_t pass_w = aw;
-    if (arena_.band_width != 0) {
-      pass_w = std::min(pass_w, arena_.band_width + 64);
-    }
-    const bool narrow_pass = pass_w <= 320;
-    if (aw <= 320) return 0;  // WB5, 384-wide ring
-    if (aw <= 575) {
-      if (narrow_pass) return 3;  // banded: WB5 passes, 576-wide ring
-      return h_desc_[w].num_seqs <= 96
-                 ? 1   // WB8, 576-wide ring, 1536-node Kahn (deep windows
-                       // can outgrow the smaller node cap; route them to
-                       // the full variant instead of bouncing via the CPU)
-                 : 2;  // WB8, full-width ring, full Kahn
-    }
-    return narrow_pass ? 4   // banded: WB5 passes, full 1024-wide ring
-                       : 2;  // WB8, full 1024-wide ring
-  };
   auto cost = [&](uint32_t w) {
     const uint32_t first = h_layer_index_[w];
     return h_layer_ends_[first + h_desc_[w].num_seqs - 1];  // total layer bytes
   };
-  // bucket reads h_desc_, which is overwritten with the sorted descriptors
+  // routing reads h_desc_, which is overwritten with the sorted descriptors
   // below — snapshot per original window up front so both the comparator and
   // the launch-range split see the pre-sort values
-  std::vector<uint32_t> bucket_of(nw0);
-  for (uint32_t i = 0; i < nw0; ++i) bucket_of[i] = bucket(i);
+  std::vector<PoaVariant> variant_of(nw0);
+  for (uint32_t i = 0; i < nw0; ++i) {
+    variant_of[i] = poa_route(h_desc_[i].max_len, h_desc_[i].num_seqs, arena_.band_width);
+  }
   std::sort(perm.begin(), perm.end(), [&](uint32_t a, uint32_t b) {
-    const uint32_t ba = bucket_of[a], bb = bucket_of[b];
-    if (ba != bb) return ba < bb;
+    const PoaVariant va = variant_of[a], vb = variant_of[b];
+    if (va != vb) return va < vb;
     const uint32_t ca = cost(a), cb = cost(b);
     if (ca != cb) return ca > cb;
     return a < b;
@@ -421,25 +316,19 @@ std::vector<bool> PoaBatch::generate(bool trim) {
   d(arena_.layer_ends_index, h_layer_index_, windows_.size() * 4);
   d(arena_.windows, h_desc_, windows_.size() * sizeof(PoaWindowDesc));
 
-  // one launch per columns-per-lane bucket over its contiguous range
-  {
-    uint32_t begin = 0;
-    while (begin < nw0) {
-      const uint32_t wb = bucket_of[perm[begin]];
-      uint32_t end = begin + 1;
-      while (end < nw0 && bucket_of[perm[end]] == wb) {
-        ++end;
-      }
-      launch_poa_kernel(arena_, begin, end - begin, wb, stream_);
-      begin = end;
+  // one launch per variant over its contiguous range
+  for (uint32_t begin = 0, end; begin < nw0; begin = end) {
+    const PoaVariant v = variant_of[perm[begin]];
+    for (end = begin + 1; end < nw0 && variant_of[perm[end]] == v; ++end) {
     }
+    launch_poa_kernel(arena_, begin, end - begin, v, stream_);
   }
 
   const size_t nw = windows_.size();
   RGA_HIP_CHECK(hipMemcpyAsync(h_consensus_, arena_.consensus,
-                               nw * limits_.max_consensus, hipMemcpyDeviceToHost, s));
+                               nw * L.max_consensus, hipMemcpyDeviceToHost, s));
   RGA_HIP_CHECK(hipMemcpyAsync(h_coverage_, arena_.coverage,
-                               nw * limits_.max_consensus * 2, hipMemcpyDeviceToHost, s));
+                               nw * L.max_consensus * 2, hipMemcpyDeviceToHost, s));
   RGA_HIP_CHECK(hipMemcpyAsync(h_consensus_len_, arena_.consensus_len, nw * 4,
                                hipMemcpyDeviceToHost, s));
   RGA_HIP_CHECK(hipMemcpyAsync(h_status_, arena_.status, nw * 4, hipMemcpyDeviceToHost, s));
@@ -448,13 +337,15 @@ std::vector<bool> PoaBatch::generate(bool trim) {
   auto t2 = clk::now();
 
   if (getenv("RGA_POA_TIMING") != nullptr) {
-    std::vector<unsigned long long> t(nw * 8);
-    RGA_HIP_CHECK(hipMemcpy(t.data(), arena_.timing, nw * 8 * 8, hipMemcpyDeviceToHost));
-    unsigned long long sum[8] = {0};
+    constexpr size_t kSlots = kPoaTimingSlots;
+    std::vector<unsigned long long> t(nw * kSlots);
+    RGA_HIP_CHECK(hipMemcpy(t.data(), arena_.timing, t.size() * sizeof(t[0]),
+                            hipMemcpyDeviceToHost));
+    unsigned long long sum[kSlots] = {0};
     std::vector<unsigned long long> totals(nw);
     for (size_t i = 0; i < nw; ++i) {
-      for (int k = 0; k < 8; ++k) sum[k] += t[i * 8 + k];
-      totals[i] = t[i * 8 + 6];
+      for (size_t k = 0; k < kSlots; ++k) sum[k] += t[i * kSlots + k];
+      totals[i] = t[i * kSlots + 6];
     }
     std::sort(totals.begin(), totals.end());
     fprintf(stderr,
@@ -474,11 +365,11 @@ std::vector<bool> PoaBatch::generate(bool trim) {
       polished[orig] = false;  // device-side failure -> CPU fallback
       continue;
     }
-    std::string consensus(reinterpret_cast<char*>(h_consensus_ + i * limits_.max_consensus),
+    std::string consensus(reinterpret_cast<char*>(h_consensus_ + i * L.max_consensus),
                           h_consensus_len_[i]);
     bool status = true;
     if (window->type() == WindowType::kTGS && trim) {
-      const uint16_t* cov = h_coverage_ + i * limits_.max_consensus;
+      const uint16_t* cov = h_coverage_ + i * L.max_consensus;
       uint32_t average = seqs_added_[orig] / 2;
       int32_t begin = 0, end = static_cast<int32_t>(consensus.size()) - 1;
       for (; begin < static_cast<int32_t>(consensus.size()); ++begin) {

@@ -53,7 +53,6 @@ class PoaBatch {
   int device_;
   void* stream_ = nullptr;
 
-  PoaLimits limits_;
   uint32_t num_slabs_;
   size_t seq_arena_cap_;
   int8_t match_, mismatch_, gap_;

@@ -36,8 +36,10 @@ namespace {
 
 constexpr int kLanes = 64;
 constexpr int32_t kNegInf = -(1 << 28);
-constexpr uint32_t kMaxW = 1024;  // LDS row width; matrix_width must fit
-constexpr uint32_t kMaxN = 2048;  // LDS graph mirrors; max_nodes must fit
+constexpr uint32_t kMaxW = kPoaLimits.matrix_width;   // DP row width (slab and widest ring)
+constexpr uint32_t kMaxN = kPoaLimits.max_nodes + 1;  // widest LDS Kahn arrays
+constexpr uint32_t kMaxE = kPoaLimits.max_edges;
+constexpr uint32_t kMaxR = kPoaLimits.max_ring;
 constexpr uint32_t kRing = 4;     // DP rows kept in LDS
 constexpr uint32_t kMaxPre = 2;   // predecessor rows precomputed per row
 
@@ -59,7 +61,7 @@ __device__ inline void wave_lds_sync() {
 // the LDS unit and dominated the DP phase — measured with RGA_POA_TIMING).
 // Sequence: shr1/2/4/8 within 16-lane rows, then bcast15 into rows 1&3 and
 // bcast31 into rows 2&3 (the classic GCN prefix idiom with max).
-__device__ inline int32_t wave_scan_max(int32_t v, int /*lane*/) {
+__device__ inline int32_t wave_scan_max(int32_t v) {
   int32_t t;
   t = __builtin_amdgcn_update_dpp(kNegInf, v, 0x111, 0xf, 0xf, false);  // row_shr:1
   v = max(v, t);
@@ -117,7 +119,7 @@ __device__ inline uint64_t pack_rd(uint8_t letter, uint8_t nin, uint16_t node,
 // co-residency.
 //
 // The ring width W is a template parameter: the kernel is instantiated per
-// width bucket (384 / 576 / 1024 columns) so the ~500-column windows of a
+// ring width of kPoaVariants so the ~500-column windows of a
 // default w=500 run pay ~7 KB of LDS (23 blocks/CU, ~5.7 waves/SIMD)
 // instead of the full-width 10.5 KB (15 blocks/CU, ~3.75/SIMD) — LDS, not
 // VGPRs (60), is the occupancy limiter.
@@ -148,27 +150,8 @@ __device__ inline int32_t poa_code(uint8_t b) {
   }
 }
 
-__device__ inline uint16_t out_edge_of(const struct WindowCtx& c, uint32_t node, uint32_t e);
-
-struct WindowCtx {
-  uint8_t* letters;
-  uint8_t* in_cnt;
-  uint8_t* out_cnt;
-  uint8_t* ring_cnt;
-  uint16_t* in_edges;
-  int32_t* in_weights;
-  uint16_t* out_edges;
-  uint16_t* ring;
-  uint16_t* nseq;
-  uint16_t* rank;
-  int64_t* hb_score;
-  int32_t* hb_pred;
-  int32_t* aln_nodes;
-  int32_t* aln_seq;
-  int16_t* matrix;
-  uint8_t* moves;
-  uint64_t* row_desc;
-
+// this window's slab pointers plus its inputs and running graph state
+struct WindowCtx : PoaSlabs {
   const uint8_t* seq_base;
   const uint8_t* weight_base;
   const uint32_t* ends;   // layer end offsets (relative to window start)
@@ -176,11 +159,7 @@ struct WindowCtx {
                           // 0xFFFFFFFF for window-spanning layers (full DP)
   uint32_t num_seqs;
 
-  uint32_t ME;  // max edges
-  uint32_t MR;  // max ring
-  uint32_t MW;  // matrix width
-  uint32_t MN;  // max nodes
-  uint32_t bw;  // 0 = full width; else static band (columns) around diagonal
+  uint32_t MN;  // node cap of the launched variant
   int32_t m, x, g;
 
   uint32_t num_nodes;
@@ -191,7 +170,7 @@ struct WindowCtx {
 // ---------- serial (lane 0) graph helpers ----------
 
 __device__ inline uint16_t out_edge_of(const WindowCtx& c, uint32_t node, uint32_t e) {
-  return c.out_edges[node * c.ME + e];
+  return c.out_edges[node * kMaxE + e];
 }
 
 __device__ inline bool add_edge_d(WindowCtx& c, uint32_t a, uint32_t b, int32_t w) {
@@ -200,29 +179,29 @@ __device__ inline bool add_edge_d(WindowCtx& c, uint32_t a, uint32_t b, int32_t 
     if (out_edge_of(c, a, e) == b) {
       uint32_t n_in = c.in_cnt[b];
       for (uint32_t f = 0; f < n_in; ++f) {
-        if (c.in_edges[b * c.ME + f] == a) {
-          c.in_weights[b * c.ME + f] += w;
+        if (c.in_edges[b * kMaxE + f] == a) {
+          c.in_weights[b * kMaxE + f] += w;
           return true;
         }
       }
       return true;  // unreachable for a consistent graph
     }
   }
-  if (n_out >= c.ME || c.in_cnt[b] >= c.ME) {
+  if (n_out >= kMaxE || c.in_cnt[b] >= kMaxE) {
     c.status = kPoaEdgeOverflow;
     return false;
   }
-  c.out_edges[a * c.ME + n_out] = static_cast<uint16_t>(b);
+  c.out_edges[a * kMaxE + n_out] = static_cast<uint16_t>(b);
   c.out_cnt[a] = static_cast<uint8_t>(n_out + 1);
   uint32_t n_in = c.in_cnt[b];
-  c.in_edges[b * c.ME + n_in] = static_cast<uint16_t>(a);
-  c.in_weights[b * c.ME + n_in] = w;
+  c.in_edges[b * kMaxE + n_in] = static_cast<uint16_t>(a);
+  c.in_weights[b * kMaxE + n_in] = w;
   c.in_cnt[b] = static_cast<uint8_t>(n_in + 1);
   return true;
 }
 
 __device__ inline int32_t add_node_d(WindowCtx& c, uint8_t letter) {
-  if (c.num_nodes >= c.MN || c.num_nodes >= kMaxN) {
+  if (c.num_nodes >= c.MN) {
     c.status = kPoaNodeOverflow;
     return -1;
   }
@@ -299,7 +278,7 @@ __device__ void add_alignment_d(WindowCtx& c, const uint8_t* seq,
       new_id = -1;
       uint32_t nr = c.ring_cnt[node];
       for (uint32_t r = 0; r < nr; ++r) {
-        uint16_t aid = c.ring[node * c.MR + r];
+        uint16_t aid = c.ring[node * kMaxR + r];
         if (c.letters[aid] == letter) {
           new_id = aid;
           break;
@@ -309,25 +288,25 @@ __device__ void add_alignment_d(WindowCtx& c, const uint8_t* seq,
         new_id = add_node_d(c, letter);
         if (new_id < 0) return;
         // join the ring: new node linked with node and all its partners
-        if (nr >= c.MR) {
+        if (nr >= kMaxR) {
           c.status = kPoaRingOverflow;
           return;
         }
         for (uint32_t r = 0; r < nr; ++r) {
-          uint16_t aid = c.ring[node * c.MR + r];
-          c.ring[new_id * c.MR + r] = aid;
+          uint16_t aid = c.ring[node * kMaxR + r];
+          c.ring[new_id * kMaxR + r] = aid;
           uint32_t arc = c.ring_cnt[aid];
-          if (arc >= c.MR) {
+          if (arc >= kMaxR) {
             c.status = kPoaRingOverflow;
             return;
           }
-          c.ring[aid * c.MR + arc] = static_cast<uint16_t>(new_id);
+          c.ring[aid * kMaxR + arc] = static_cast<uint16_t>(new_id);
           c.ring_cnt[aid] = static_cast<uint8_t>(arc + 1);
         }
-        c.ring[new_id * c.MR + nr] = static_cast<uint16_t>(node);
+        c.ring[new_id * kMaxR + nr] = static_cast<uint16_t>(node);
         c.ring_cnt[new_id] = static_cast<uint8_t>(nr + 1);
         uint32_t nrc = c.ring_cnt[node];
-        c.ring[node * c.MR + nrc] = static_cast<uint16_t>(new_id);
+        c.ring[node * kMaxR + nrc] = static_cast<uint16_t>(new_id);
         c.ring_cnt[node] = static_cast<uint8_t>(nrc + 1);
       }
     }
@@ -407,8 +386,8 @@ __device__ int32_t consensus_d(WindowCtx& c, SH& s, uint8_t* out, uint16_t* cov,
     uint16_t nid = s.u.kahn.queue[r];
     uint32_t nin = c.in_cnt[nid];
     for (uint32_t e = 0; e < nin; ++e) {
-      uint16_t p = c.in_edges[nid * c.ME + e];
-      int64_t w = c.in_weights[nid * c.ME + e];
+      uint16_t p = c.in_edges[nid * kMaxE + e];
+      int64_t w = c.in_weights[nid * kMaxE + e];
       if (c.hb_score[nid] < w ||
           (c.hb_score[nid] == w && c.hb_pred[nid] != -1 &&
            c.hb_score[c.hb_pred[nid]] <= c.hb_score[p])) {
@@ -442,7 +421,7 @@ __device__ int32_t consensus_d(WindowCtx& c, SH& s, uint8_t* out, uint16_t* cov,
       uint16_t endn = out_edge_of(c, max_id, e);
       uint32_t nin = c.in_cnt[endn];
       for (uint32_t f = 0; f < nin; ++f) {
-        uint16_t o = c.in_edges[endn * c.ME + f];
+        uint16_t o = c.in_edges[endn * kMaxE + f];
         if (o != max_id) {
           c.hb_score[o] = -1;
         }
@@ -456,11 +435,11 @@ __device__ int32_t consensus_d(WindowCtx& c, SH& s, uint8_t* out, uint16_t* cov,
       c.hb_pred[nid] = -1;
       uint32_t nin = c.in_cnt[nid];
       for (uint32_t e = 0; e < nin; ++e) {
-        uint16_t p = c.in_edges[nid * c.ME + e];
+        uint16_t p = c.in_edges[nid * kMaxE + e];
         if (c.hb_score[p] == -1) {
           continue;
         }
-        int64_t w = c.in_weights[nid * c.ME + e];
+        int64_t w = c.in_weights[nid * kMaxE + e];
         if (c.hb_score[nid] < w ||
             (c.hb_score[nid] == w && c.hb_pred[nid] != -1 &&
              c.hb_score[c.hb_pred[nid]] <= c.hb_score[p])) {
@@ -497,7 +476,7 @@ __device__ int32_t consensus_d(WindowCtx& c, SH& s, uint8_t* out, uint16_t* cov,
     uint32_t covv = c.nseq[node];
     uint32_t nr = c.ring_cnt[node];
     for (uint32_t r = 0; r < nr; ++r) {
-      covv += c.nseq[c.ring[node * c.MR + r]];
+      covv += c.nseq[c.ring[node * kMaxR + r]];
     }
     cov[k] = static_cast<uint16_t>(min(covv, 65535u));
     idw = c.hb_pred[idw];
@@ -514,7 +493,7 @@ __device__ void build_row_desc(WindowCtx& c, int lane) {
     const uint8_t nin = c.in_cnt[node];
     uint16_t pred_row = 0;
     if (nin > 0) {
-      pred_row = static_cast<uint16_t>(c.rank[c.in_edges[node * c.ME]] + 1);
+      pred_row = static_cast<uint16_t>(c.rank[c.in_edges[node * kMaxE]] + 1);
     }
     const uint32_t nout = c.out_cnt[node];
     uint8_t flags = (nout == 0) ? kRdEnd : 0;
@@ -529,14 +508,581 @@ __device__ void build_row_desc(WindowCtx& c, int lane) {
   }
 }
 
+// ---------- lane-parallel phases ----------
+
+// Graph of the backbone alone (layer 0): a chain, already in topological
+// order, with its row descriptors.
+template <class SH>
+__device__ void init_backbone_d(WindowCtx& c, SH& s, int lane) {
+  const uint32_t bb_len = c.ends[0];
+  const uint8_t* bb_seq = c.seq_base;
+  const uint8_t* bb_wts = c.weight_base;
+  for (uint32_t i = lane; i < bb_len; i += kLanes) {
+    c.letters[i] = bb_seq[i];
+    c.ring_cnt[i] = 0;
+    c.nseq[i] = bb_len >= 2 ? 1 : 0;
+    // queue holds the trivial order for the no-aligned-layer case (it is
+    // clobbered by the DP ring and rebuilt by every topo sort afterwards)
+    s.u.kahn.queue[i] = static_cast<uint16_t>(i);
+    c.rank[i] = static_cast<uint16_t>(i);
+    uint8_t nin = 0;
+    if (i == 0) {
+      c.in_cnt[i] = 0;
+    } else {
+      nin = 1;
+      c.in_cnt[i] = 1;
+      c.in_edges[i * kMaxE] = static_cast<uint16_t>(i - 1);
+      c.in_weights[i * kMaxE] = static_cast<int32_t>(bb_wts[i - 1]) + bb_wts[i];
+    }
+    uint8_t flags = 0;
+    if (i + 1 < bb_len) {
+      c.out_cnt[i] = 1;
+      c.out_edges[i * kMaxE] = static_cast<uint16_t>(i + 1);
+    } else {
+      c.out_cnt[i] = 0;
+      flags = kRdEnd;
+    }
+    c.row_desc[i] = pack_rd(bb_seq[i], nin, static_cast<uint16_t>(i),
+                            static_cast<uint16_t>(i), flags);
+  }
+  c.num_nodes = bb_len;
+  c.seqs_in_graph = 1;
+  __syncthreads();  // graph writes -> visible to all lanes
+}
+
+// Per-layer match bitvectors (see Shared::match) straight from the
+// (L2-resident) global layer bytes, lane-parallel over chunk words; one
+// spare zero word so cross-word extraction never reads out of bounds.
+template <class SH>
+__device__ void build_match_bits_d(SH& s, const uint8_t* seq, uint32_t len, int lane) {
+  const uint32_t words = (len + kLanes - 1) / kLanes + 1;
+  for (uint32_t w = lane; w < words * 4; w += kLanes) {
+    const uint32_t k = w >> 2, cc = w & 3;
+    uint64_t bits = 0;
+    const uint32_t base = k * kLanes;
+    if (base < len) {
+      const uint32_t lim = min(kLanes, len - base);
+      for (uint32_t l = 0; l < lim; ++l) {
+        if (poa_code(seq[base + l]) == static_cast<int32_t>(cc)) {
+          bits |= 1ull << l;
+        }
+      }
+    }
+    s.match[cc][k] = bits;
+  }
+  __syncthreads();
+}
+
+// What one layer's DP rows share.
+struct LayerDp {
+  const uint8_t* seq;
+  uint32_t len;
+  uint32_t chunks;  // 64-column chunks covering len
+  // SUBGRAPH restriction (CPU parity, Window::generate_consensus): a
+  // layer that does not span the window aligns only against the rank
+  // window [rank(backbone[begin]), rank(backbone[end])]. Rows outside are
+  // skipped, predecessor edges from below rank(begin) are ignored (rows
+  // losing every predecessor become NW start rows), and the alignment
+  // target is the span's end rank (plus true sinks inside the window).
+  // The reference's cudapoa aligns every layer to the full graph instead,
+  // which is what degrades its long-window GPU goldens (racon_test.cpp
+  // pins 4168 vs CPU 1289 at w=1000); this engine keeps the CPU
+  // windowing semantics on device.
+  bool sub;
+  uint32_t rlo, rhi;
+  // banded mode (-b): static band of bw columns around the rank diagonal of
+  // the (possibly rank-restricted) row window
+  bool banded;
+  uint32_t bw;
+  uint32_t slope16;
+};
+
+// DP row (rank + 1) of in-edge e's source node; the first kMaxPre are
+// precomputed once per row, beyond that re-derived on use (nodes with that
+// many in-edges are rare).
+__device__ __forceinline__ uint32_t pred_row_of(const WindowCtx& c, uint32_t node, uint32_t e,
+                                                const uint32_t (&pred_rows)[kMaxPre]) {
+  return (e < kMaxPre) ? pred_rows[e] : c.rank[c.in_edges[node * kMaxE + e]] + 1;
+}
+
+// Columns of banded DP row p that hold a value: [lo + 1, hi], plus column 0
+// when has0.
+struct PredBand {
+  uint32_t lo, hi;
+  bool has0;
+};
+
+__device__ __forceinline__ PredBand pred_band(const LayerDp& d, uint32_t p) {
+  uint32_t pklo, pkhi;
+  band_chunks(p - d.rlo, d.slope16, d.bw, d.chunks, &pklo, &pkhi);
+  return {pklo * kLanes, min(d.len, (pkhi + 1) * kLanes), pklo == 0};
+}
+
+// Gathers pv[w] = row(cbase + w), w in 0..WB, with columns outside okmask
+// set to -inf; `last` is the row's last addressable column. Loads are
+// UNCONDITIONAL with a clamped index + VALU select: per-element predication
+// compiled to one exec-branched flat_load each (generic pointer),
+// serializing the row. Called once for an LDS ring row and once for a
+// global matrix row; each call must keep its address space (ds_read vs
+// global_load), and that is brittle: `row` is a functor indexing the
+// caller's own array expression, and each load is selected where it is
+// made, because with a plain `const int16_t*` parameter, or with the loads
+// first and one select loop after them, the compiler merged the tails of the
+// two calls into flat_loads (1-6 per kernel). Re-check the ISA for flat_load
+// after touching this.
+template <uint32_t WB, class Row>
+__device__ __forceinline__ void gather_row(const Row& row, uint32_t cbase, uint32_t last,
+                                           uint32_t okmask, int32_t (&pv)[WB + 1]) {
+  if constexpr (WB == 8) {
+    if (cbase + WB <= last) {
+      // unpack a 16-byte vector load into pv[0..7] (cbase*2 is a
+      // multiple of 16 when WB == 8, and both the ring rows and the
+      // global matrix rows are 16-byte aligned); replaces 8 scalar
+      // b16 loads — the LDS pipe is the congested unit at 20+
+      // co-resident windows per CU (profiles/PARKED.md)
+      const int4 v = *reinterpret_cast<const int4*>(&row(cbase));
+      const int32_t ws[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+      for (uint32_t q = 0; q < 4; ++q) {
+        pv[2 * q] = static_cast<int32_t>(static_cast<int16_t>(ws[q] & 0xffff));
+        pv[2 * q + 1] = ws[q] >> 16;  // arithmetic: sign-extended
+      }
+      pv[WB] = row(cbase + WB);
+#pragma unroll
+      for (uint32_t w = 0; w <= WB; ++w) {
+        pv[w] = ((okmask >> w) & 1u) ? pv[w] : kNegInf;
+      }
+      return;
+    }
+  }
+  if (cbase + WB <= last) {
+#pragma unroll
+    for (uint32_t w = 0; w <= WB; ++w) {
+      const int32_t val = row(cbase + w);
+      pv[w] = ((okmask >> w) & 1u) ? val : kNegInf;
+    }
+  } else {
+#pragma unroll
+    for (uint32_t w = 0; w <= WB; ++w) {
+      const int32_t val = row(min(cbase + w, last));
+      pv[w] = ((okmask >> w) & 1u) ? val : kNegInf;
+    }
+  }
+}
+
+// One DP row: rank r of the topological order (matrix row r + 1) against
+// the whole layer, all lanes. Row 0 (all-gap) is arithmetic: H0[j] = j * g —
+// never materialized. Updates the running alignment end (best_score,
+// best_row), which stays wave-uniform. The context comes BY VALUE: the row
+// only reads it, and taken by reference the whole struct stayed in scratch
+// memory (208 B/lane on every variant).
+template <uint32_t WB, uint32_t MAXW, class SH>
+__device__ __forceinline__ void dp_row(const WindowCtx c, SH& s, const LayerDp& d, uint32_t r,
+                                       uint64_t rd, int lane, int32_t& best_score,
+                                       uint32_t& best_row) {
+  const uint32_t len = d.len;
+  const uint8_t letter = static_cast<uint8_t>(rd);
+  const int32_t letter_code = poa_code(letter);
+  const uint32_t nin = static_cast<uint32_t>((rd >> 8) & 0xff);
+  const uint32_t node = static_cast<uint32_t>((rd >> 16) & 0xffff);
+  const uint32_t pred0 = static_cast<uint32_t>((rd >> 32) & 0xffff);
+  const uint64_t flags = (rd >> 48) & 0xff;
+  const bool is_end = (flags & kRdEnd) != 0;
+  const bool store_row = (flags & kRdStore) != 0;
+  int16_t* Hrow = c.matrix + static_cast<size_t>(r + 1) * kMaxW;
+  uint8_t* Mrow = c.moves + static_cast<size_t>(r + 1) * kMaxW;
+  int16_t* ring_row = s.u.ring[(r + 1) % kRing];
+
+  uint32_t pred_rows[kMaxPre];  // see pred_row_of
+  pred_rows[0] = pred0;
+  const uint32_t npre = min(nin, kMaxPre);
+  for (uint32_t e = 1; e < npre; ++e) {
+    pred_rows[e] = c.rank[c.in_edges[node * kMaxE + e]] + 1;
+  }
+
+  // usable predecessor edges: in subgraph mode edges from ranks below
+  // the window are cut; a row losing every predecessor becomes an NW
+  // start row (virtual row 0), matching the CPU subgraph's sources.
+  // Edge index 63 in a move byte encodes that virtual start for the
+  // traceback (real indices stop at max_edges-1 = 47).
+  uint64_t usable = (1ull << nin) - 1;  // nin <= 48 < 64
+  if (d.sub && nin != 0) {
+    usable = 0;
+    for (uint32_t e = 0; e < nin; ++e) {
+      if (pred_row_of(c, node, e, pred_rows) > d.rlo) {
+        usable |= 1ull << e;
+      }
+    }
+  }
+  const bool vstart = usable == 0;  // nin == 0, or every pred cut
+
+  uint32_t row_klo = 0, row_khi = d.chunks - 1;
+  if (d.banded) {
+    band_chunks(r + 1 - d.rlo, d.slope16, d.bw, d.chunks, &row_klo, &row_khi);
+  }
+
+  // fetch a predecessor row value: LDS ring if close, global otherwise;
+  // in banded mode, columns outside the predecessor's band are -inf
+  auto pred_val = [&](uint32_t p, uint32_t col) -> int32_t {
+    if (p == 0) {
+      return static_cast<int32_t>(col) * c.g;  // arithmetic row 0
+    }
+    if (d.banded) {
+      const PredBand pb = pred_band(d, p);
+      if (col == 0 ? !pb.has0 : (col <= pb.lo || col > pb.hi)) {
+        return kNegInf;
+      }
+    }
+    if (r + 1 - p < kRing) {
+      return s.u.ring[p % kRing][col];
+    }
+    return c.matrix[static_cast<size_t>(p) * kMaxW + col];
+  };
+
+  // first column (j = 0): max over preds of Hp[0] + gap
+  // (banded: only when this row's band includes column 0)
+  int32_t h0 = kNegInf;
+  uint32_t e0 = 0;
+  if (row_klo == 0) {
+    int32_t best0 = kNegInf;
+    if (vstart) {
+      best0 = 0;
+      e0 = 63;  // virtual-start sentinel (see `usable`)
+    } else {
+      for (uint32_t e = 0; e < nin; ++e) {
+        if (!((usable >> e) & 1)) {
+          continue;
+        }
+        const int32_t hp0 = pred_val(pred_row_of(c, node, e, pred_rows), 0);
+        if (hp0 > best0) {
+          best0 = hp0;
+          e0 = e;
+        }
+      }
+    }
+    h0 = best0 + c.g;
+    if (lane == 0) {
+      if (store_row) {
+        Hrow[0] = static_cast<int16_t>(h0);
+      }
+      ring_row[0] = static_cast<int16_t>(h0);
+      // column 0 is always a vertical chain through the argmax edge
+      // (moves layout is shifted: col j lives at j-1, col 0 at kMaxW-1,
+      // so each lane's 8 move bytes form one aligned u64 store)
+      Mrow[kMaxW - 1] = static_cast<uint8_t>(kMvUp | (e0 << 2));
+    }
+  }
+
+  // ---- lane-blocked columns ----
+  // Lane l owns WB contiguous columns per pass; one register-local
+  // inclusive scan + one DPP wave scan per pass replaces the previous
+  // chunk-serial carry chain (8 dependent LDS+scan segments per row).
+  const uint32_t j0 = d.banded ? row_klo * kLanes : 0;
+  const uint32_t jend = d.banded ? min(len, (row_khi + 1) * kLanes) : len;
+  int32_t carry_u = h0;  // u-space max through column j0 (h0 = -inf when
+                         // the band excludes column 0)
+  int32_t last_col_val = kNegInf;
+  int32_t pass_tail = 0;  // lane 63's last clamped value of the previous
+                          // pass (the shifted store's column `base`)
+
+  for (uint32_t base = j0; base < jend; base += kLanes * WB) {
+    const uint32_t cbase = base + lane * WB;  // own cols: cbase+1..cbase+WB
+    const uint32_t nown = (cbase < jend) ? min(WB, jend - cbase) : 0;
+
+    // substitution matches for own columns: bits w of mbits
+    uint64_t mbits = 0;
+    if (letter_code >= 0 && nown > 0) {
+      const uint32_t bit0 = cbase & 63;
+      const uint32_t w0 = cbase >> 6;
+      mbits = s.match[letter_code][w0] >> bit0;
+      if (bit0 != 0) {
+        mbits |= s.match[letter_code][w0 + 1] << (64 - bit0);
+      }
+    } else if (nown > 0) {
+      for (uint32_t w = 0; w < nown; ++w) {
+        if (d.seq[cbase + w] == letter) {  // rare: non-ACGT row letter
+          mbits |= 1ull << w;
+        }
+      }
+    }
+
+    int32_t bd[WB], bu[WB];  // best diagonal / vertical candidates
+#pragma unroll
+    for (uint32_t w = 0; w < WB; ++w) {
+      bd[w] = kNegInf;
+      bu[w] = kNegInf;
+    }
+
+    if (vstart) {
+#pragma unroll
+      for (uint32_t w = 0; w < WB; ++w) {
+        if (w < nown) {
+          const int32_t j = static_cast<int32_t>(cbase + 1 + w);
+          const int32_t subst = ((mbits >> w) & 1) ? c.m : c.x;
+          bd[w] = (j - 1) * c.g + subst;
+          bu[w] = j * c.g + c.g;
+        }
+      }
+    } else {
+      for (uint32_t e = 0; e < nin; ++e) {
+        if (!((usable >> e) & 1)) {
+          continue;
+        }
+        const uint32_t p = pred_row_of(c, node, e, pred_rows);
+        int32_t pv[WB + 1];  // pred row values pv[w] = H(p, cbase + w)
+        if (p == 0) {
+#pragma unroll
+          for (uint32_t w = 0; w <= WB; ++w) {
+            pv[w] = static_cast<int32_t>(cbase + w) * c.g;
+          }
+        } else {
+          PredBand pb{0, len, true};
+          if (d.banded) {
+            pb = pred_band(d, p);
+          }
+          // validity of the contiguous range [lo+1, hi] (plus col 0
+          // when the pred row computed it) hoisted into ONE bitmask per
+          // edge — per-element compare+select chains were ~10% of the
+          // kernel's VALU issue
+          const uint32_t lo_col = pb.lo + 1;
+          const uint32_t lo_w = lo_col > cbase ? min(lo_col - cbase, WB + 1) : 0;
+          const uint32_t hi_w = (pb.hi + 1 > cbase) ? min(pb.hi + 1 - cbase, WB + 1) : 0;
+          uint32_t okmask = (hi_w > lo_w) ? ((1u << hi_w) - (1u << lo_w)) : 0u;
+          if (cbase == 0 && pb.has0) {
+            okmask |= 1u;  // col 0 sits outside [lo+1, hi] by construction
+          }
+          if (r + 1 - p < kRing) {
+            const uint32_t slot = p % kRing;
+            gather_row<WB>([&](uint32_t col) -> const int16_t& { return s.u.ring[slot][col]; },
+                           cbase, MAXW - 1, okmask, pv);
+          } else {
+            const int16_t* gsrc = c.matrix + static_cast<size_t>(p) * kMaxW;
+            gather_row<WB>([&](uint32_t col) -> const int16_t& { return gsrc[col]; }, cbase,
+                           kMaxW - 1, okmask, pv);
+          }
+        }
+        // no nown guard: out-of-range pv entries are -inf and propagate
+#pragma unroll
+        for (uint32_t w = 0; w < WB; ++w) {
+          const int32_t subst = ((mbits >> w) & 1) ? c.m : c.x;
+          bd[w] = max(bd[w], pv[w] + subst);
+          bu[w] = max(bu[w], pv[w + 1] + c.g);
+        }
+      }
+    }
+
+    // local inclusive u-space scan over own columns (out-of-range
+    // candidates are already -inf; no per-element guard needed)
+    int32_t us[WB];
+    int32_t run = kNegInf;
+#pragma unroll
+    for (uint32_t w = 0; w < WB; ++w) {
+      const int32_t j = static_cast<int32_t>(cbase + 1 + w);
+      const int32_t u = max(bd[w], bu[w]) - j * c.g;
+      run = max(run, u);
+      us[w] = run;
+    }
+    // wave scan over lane totals -> exclusive prefix for this lane
+    const int32_t incl = wave_scan_max(run);
+    int32_t excl =
+        __builtin_amdgcn_update_dpp(kNegInf, incl, 0x138, 0xf, 0xf, false);  // wave_shr:1
+    excl = max(excl, carry_u);
+    // next pass's carry: wave-uniform max over everything <= this pass
+    carry_u = max(carry_u, __builtin_amdgcn_readlane(incl, kLanes - 1));
+
+    // finalize own columns: h, moves, stores. h is computed for every
+    // slot (junk past the row end feeds only junk columns); the move
+    // logic stays guarded.
+    int32_t h_sel = kNegInf;
+    uint64_t mvpack = 0;  // 8 move bytes -> one aligned store at Mrow[cbase]
+    int32_t harr[WB];
+#pragma unroll
+    for (uint32_t w = 0; w < WB; ++w) {
+      const uint32_t j = cbase + 1 + w;
+      const int32_t v = max(bd[w], bu[w]);
+      const int32_t h = max(us[w], excl) + static_cast<int32_t>(j) * c.g;
+      harr[w] = h < -28000 ? -28000 : h;
+      if (w < nown) {
+        uint8_t mv;
+        if (h != v) {
+          mv = kMvLeft;
+        } else if (vstart) {
+          mv = static_cast<uint8_t>(((bd[w] >= bu[w]) ? kMvDiag : kMvUp) | (63u << 2));
+        } else if (nin == 1) {
+          mv = (bd[w] >= bu[w]) ? kMvDiag : kMvUp;
+        } else {
+          // rare multi-pred row: recover the argmax edge (first e wins)
+          const uint8_t type = (bd[w] >= bu[w]) ? kMvDiag : kMvUp;
+          const int32_t want = (type == kMvDiag) ? bd[w] : bu[w];
+          uint32_t esel = 0;
+          const int32_t subst = ((mbits >> w) & 1) ? c.m : c.x;
+          for (uint32_t e = 0; e < nin; ++e) {
+            if (!((usable >> e) & 1)) {
+              continue;
+            }
+            const uint32_t p = pred_row_of(c, node, e, pred_rows);
+            const int32_t cand =
+                (type == kMvDiag) ? pred_val(p, j - 1) + subst : pred_val(p, j) + c.g;
+            if (cand == want) {
+              esel = e;
+              break;
+            }
+          }
+          mv = static_cast<uint8_t>(type | (esel << 2));
+        }
+        if (WB == 8) {
+          mvpack |= static_cast<uint64_t>(mv) << (8 * w);
+        } else {
+          if (store_row) {
+            Hrow[j] = static_cast<int16_t>(harr[w]);
+          }
+          ring_row[j] = static_cast<int16_t>(harr[w]);
+          Mrow[j - 1] = mv;  // shifted layout, per-byte for odd widths
+        }
+        if (j == len) {
+          h_sel = h;
+        }
+      }
+    }
+    if (WB == 8) {
+      // Shifted 16-byte row stores: lane l writes columns
+      // [cbase .. cbase+7] = [neighbor's last value | own h[0..6]] so
+      // the store is one aligned b128 instead of 8 b16 ops (LDS-pipe
+      // congestion is the bottleneck — profiles/PARKED.md). Column
+      // `base` comes from lane 63 of the previous pass (or h0), the
+      // pass-boundary column base+512 from the NEXT pass's lane 0, and
+      // a row ending exactly on the boundary stores it explicitly.
+      const int32_t tail_in = (base == j0) ? h0 : pass_tail;
+      const int32_t shifted =
+          __builtin_amdgcn_update_dpp(tail_in, harr[WB - 1], 0x138, 0xf, 0xf, false);
+      pass_tail = __builtin_amdgcn_readlane(harr[WB - 1], kLanes - 1);
+      if (cbase < jend) {
+        int4 vec;
+        vec.x = (shifted & 0xffff) | (harr[0] << 16);
+        vec.y = (harr[1] & 0xffff) | (harr[2] << 16);
+        vec.z = (harr[3] & 0xffff) | (harr[4] << 16);
+        vec.w = (harr[5] & 0xffff) | (harr[6] << 16);
+        *reinterpret_cast<int4*>(&ring_row[cbase]) = vec;
+        if (store_row) {
+          *reinterpret_cast<int4*>(Hrow + cbase) = vec;
+        }
+      }
+      // When this pass's last covered column is `len` itself AND len
+      // lands on a lane boundary ((len - base) % WB == 0), the lane
+      // that would store it via its shifted slot has cbase == len and
+      // is excluded by the cbase < jend guard — store it explicitly
+      // from the owning lane's last value. (Missing this for ANY
+      // multiple-of-8 row length left ring[len] uninitialized and made
+      // results depend on stale LDS — caught by tools/probe_order.py.)
+      const uint32_t rem = len > base ? len - base : 0;
+      if (rem > 0 && rem <= kLanes * WB && (rem & (WB - 1)) == 0) {
+        const int owner = static_cast<int>(rem / WB) - 1;
+        const int32_t t16 = __builtin_amdgcn_readlane(harr[WB - 1], owner);
+        if (lane == 0) {
+          ring_row[len] = static_cast<int16_t>(t16);
+          if (store_row) {
+            Hrow[len] = static_cast<int16_t>(t16);
+          }
+        }
+      }
+    }
+    if (WB == 8 && cbase < len) {
+      if (cbase + WB < kMaxW) {
+        // one aligned u64 store covers the lane's 8 move bytes
+        // (cbase is a multiple of 8 exactly when WB == 8); bytes beyond
+        // nown encode columns past the row end and are never read back
+        *reinterpret_cast<uint64_t*>(Mrow + cbase) = mvpack;
+      } else {
+        // near-full row: byte kMaxW-1 is the shifted column-0 slot (stored
+        // above as kMvUp); a packed store here would clobber it with the
+        // padding byte 0 (kMvDiag) and derail the traceback at j==0.
+        // Store only the live bytes individually.
+        for (uint32_t w = 0; w < nown; ++w) {
+          Mrow[cbase + w] = static_cast<uint8_t>(mvpack >> (8 * w));
+        }
+      }
+    }
+    if (len > base && len <= base + kLanes * WB) {
+      const int owner = static_cast<int>((len - 1 - base) / WB);
+      last_col_val = __builtin_amdgcn_readlane(h_sel, owner);
+    }
+  }
+
+  // ring writes must be visible to every lane before the next row;
+  // deliberately NOT __syncthreads (would drain the global row stores)
+  wave_lds_sync();
+
+  // end-node max (strict >, first in topological order wins);
+  // last_col_val is already wave-uniform (readlane). In subgraph mode
+  // the span's end rank is the alignment sink (plus true sinks inside
+  // the window).
+  if ((is_end || (d.sub && r == d.rhi)) && last_col_val > best_score) {
+    best_score = last_col_val;
+    best_row = r + 1;
+  }
+}
+
+// ---------- serial (lane 0) traceback ----------
+
+// Walks the move bytes back from (best_row, len) to the origin; writes the
+// path (reversed) into aln_nodes / aln_seq and returns its length.
+__device__ int32_t traceback_d(WindowCtx& c, uint32_t best_row, uint32_t len) {
+  int32_t aln_len = 0;
+  uint32_t i = best_row, j = len;
+  while (!(i == 0 && j == 0)) {
+    uint32_t prev_i = i, prev_j = j;
+    int32_t rec_node = -1, rec_seq = -1;
+    if (i == 0) {
+      // row 0: all-gap prefix — consume remaining columns
+      rec_seq = static_cast<int32_t>(j - 1);
+      prev_j = j - 1;
+    } else {
+      const uint8_t mv = c.moves[static_cast<size_t>(i) * kMaxW + (j != 0 ? j - 1 : kMaxW - 1)];
+      const uint8_t type = mv & 3;
+      const uint32_t e = mv >> 2;
+      const uint64_t rd = c.row_desc[i - 1];
+      const uint32_t node = static_cast<uint32_t>((rd >> 16) & 0xffff);
+      const uint32_t nin = static_cast<uint32_t>((rd >> 8) & 0xff);
+      if (type == kMvLeft) {
+        rec_seq = static_cast<int32_t>(j - 1);
+        prev_j = j - 1;
+      } else {
+        uint32_t p = 0;  // virtual row 0: genuine start rows (nin==0)
+                         // and subgraph sources (edge sentinel 63)
+        if (nin != 0 && e != 63) {
+          p = (e == 0) ? static_cast<uint32_t>((rd >> 32) & 0xffff)
+                       : c.rank[c.in_edges[node * kMaxE + e]] + 1;
+        }
+        if (type == kMvDiag) {
+          rec_node = static_cast<int32_t>(node);
+          rec_seq = static_cast<int32_t>(j - 1);
+          prev_i = p;
+          prev_j = j - 1;
+        } else if (type == kMvUp) {
+          rec_node = static_cast<int32_t>(node);
+          prev_i = p;
+        } else {
+          c.status = kPoaConsensusOverflow;  // invalid move: fail window
+          break;
+        }
+      }
+    }
+    c.aln_nodes[aln_len] = rec_node;
+    c.aln_seq[aln_len] = rec_seq;
+    ++aln_len;
+    i = prev_i;
+    j = prev_j;
+  }
+  return aln_len;
+}
+
 // ---------- the mega-kernel ----------
 
 // MINWAVES is the occupancy the compiler must budget registers for
 // (waves/SIMD floor): the 8-wide variants otherwise help themselves to the
 // full 128-VGPR budget of 4 waves/SIMD and registers — not LDS — become
 // the residency limiter.
-template <bool TIMED, uint32_t WB, uint32_t MAXW, uint32_t MAXN = kMaxN,
-          uint32_t MINWAVES = 4>
+template <bool TIMED, uint32_t WB, uint32_t MAXW, uint32_t MAXN, uint32_t MINWAVES>
 __launch_bounds__(kLanes, MINWAVES)
 __global__ void poa_window_kernel(PoaDeviceArena a, uint32_t window_base,
                                   uint32_t num_windows) {
@@ -548,35 +1094,16 @@ __global__ void poa_window_kernel(PoaDeviceArena a, uint32_t window_base,
   const uint32_t win = window_base + blockIdx.x;
   const int lane = threadIdx.x;
   const PoaWindowDesc desc = a.windows[win];
-  // the capacity model is fixed (PoaLimits defaults; PoaBatch never alters
-  // it) — compile-time limits keep slab addressing in immediates instead of
-  // ~100 live SGPRs that were spilling into v_readlane/writelane traffic in
-  // the DP row loop
-  constexpr PoaLimits L{};
-  const uint32_t slab = desc.scratch_idx;
 
   __shared__ Shared<MAXW, MAXN> s;
 
   WindowCtx c;
-  c.letters = a.letters + static_cast<size_t>(slab) * L.max_nodes;
-  c.in_cnt = a.in_cnt + static_cast<size_t>(slab) * L.max_nodes;
-  c.out_cnt = a.out_cnt + static_cast<size_t>(slab) * L.max_nodes;
-  c.ring_cnt = a.ring_cnt + static_cast<size_t>(slab) * L.max_nodes;
-  c.in_edges = a.in_edges + static_cast<size_t>(slab) * L.max_nodes * L.max_edges;
-  c.in_weights = a.in_weights + static_cast<size_t>(slab) * L.max_nodes * L.max_edges;
-  c.out_edges = a.out_edges + static_cast<size_t>(slab) * L.max_nodes * L.max_edges;
-  c.ring = a.ring + static_cast<size_t>(slab) * L.max_nodes * L.max_ring;
-  c.nseq = a.nseq + static_cast<size_t>(slab) * L.max_nodes;
-  c.rank = a.rank + static_cast<size_t>(slab) * L.max_nodes;
-  c.hb_score = a.hb_score + static_cast<size_t>(slab) * L.max_nodes;
-  c.hb_pred = a.hb_pred + static_cast<size_t>(slab) * L.max_nodes;
-  c.aln_nodes = a.aln_nodes + static_cast<size_t>(slab) * (2 * L.matrix_width + L.max_nodes);
-  c.aln_seq = a.aln_seq + static_cast<size_t>(slab) * (2 * L.matrix_width + L.max_nodes);
-  c.matrix = a.matrix + static_cast<size_t>(slab) * (L.max_nodes + 1) * L.matrix_width;
-  c.moves = a.moves + static_cast<size_t>(slab) * (L.max_nodes + 1) * L.matrix_width;
-  c.row_desc = a.row_desc + static_cast<size_t>(slab) * L.max_nodes;
+  static_cast<PoaSlabs&>(c) = a.slabs;
+  for_each_poa_slab(c, [slab = static_cast<size_t>(desc.scratch_idx)](auto*& p, size_t count) {
+    p += slab * count;
+  });
 
-  unsigned long long* timing = a.timing + static_cast<size_t>(win) * 8;
+  unsigned long long* timing = a.timing + static_cast<size_t>(win) * kPoaTimingSlots;
   unsigned long long tick = TIMED ? wall_clock64() : 0;
   const unsigned long long t_start = tick;
   unsigned long long t_dp = 0, t_tb = 0, t_add = 0, t_topo = 0, t_rd = 0, t_cons = 0;
@@ -596,51 +1123,13 @@ __global__ void poa_window_kernel(PoaDeviceArena a, uint32_t window_base,
   c.ends = a.layer_ends + a.layer_ends_index[win];
   c.spans = a.layer_spans + a.layer_ends_index[win];
   c.num_seqs = desc.num_seqs;
-  c.ME = L.max_edges;
-  c.MR = L.max_ring;
-  c.MW = L.matrix_width;
-  c.MN = min(L.max_nodes, MAXN - 1);  // variant Kahn capacity (see Shared)
-  c.bw = a.band_width;
+  c.MN = MAXN - 1;  // variant Kahn capacity (see Shared)
   c.m = a.match;
   c.x = a.mismatch;
   c.g = a.gap;
-  c.status = (L.matrix_width <= kMaxW && L.max_nodes <= kMaxN) ? kPoaOk : kPoaNodeOverflow;
+  c.status = kPoaOk;
 
-  // ---- init graph from the backbone (layer 0), lane-parallel ----
-  const uint32_t bb_len = c.ends[0];
-  const uint8_t* bb_seq = c.seq_base;
-  const uint8_t* bb_wts = c.weight_base;
-  for (uint32_t i = lane; i < bb_len; i += kLanes) {
-    c.letters[i] = bb_seq[i];
-    c.ring_cnt[i] = 0;
-    c.nseq[i] = bb_len >= 2 ? 1 : 0;
-    // queue holds the trivial order for the no-aligned-layer case (it is
-    // clobbered by the DP ring and rebuilt by every topo sort afterwards)
-    s.u.kahn.queue[i] = static_cast<uint16_t>(i);
-    c.rank[i] = static_cast<uint16_t>(i);
-    uint8_t nin = 0;
-    if (i == 0) {
-      c.in_cnt[i] = 0;
-    } else {
-      nin = 1;
-      c.in_cnt[i] = 1;
-      c.in_edges[i * c.ME] = static_cast<uint16_t>(i - 1);
-      c.in_weights[i * c.ME] = static_cast<int32_t>(bb_wts[i - 1]) + bb_wts[i];
-    }
-    uint8_t flags = 0;
-    if (i + 1 < bb_len) {
-      c.out_cnt[i] = 1;
-      c.out_edges[i * c.ME] = static_cast<uint16_t>(i + 1);
-    } else {
-      c.out_cnt[i] = 0;
-      flags = kRdEnd;
-    }
-    c.row_desc[i] = pack_rd(bb_seq[i], nin, static_cast<uint16_t>(i),
-                            static_cast<uint16_t>(i), flags);
-  }
-  c.num_nodes = bb_len;
-  c.seqs_in_graph = 1;
-  __syncthreads();  // graph writes -> visible to all lanes
+  init_backbone_d(c, s, lane);
 
   // ---- per-layer loop ----
   for (uint32_t layer = 1; layer < c.num_seqs && c.status == kPoaOk; ++layer) {
@@ -648,511 +1137,48 @@ __global__ void poa_window_kernel(PoaDeviceArena a, uint32_t window_base,
     const uint32_t len = c.ends[layer] - beg;
     const uint8_t* seq = c.seq_base + beg;
     const uint8_t* wts = c.weight_base + beg;
-    if (len == 0) {
+    if (len == 0 || len + 1 > kMaxW) {
       continue;  // host should have filtered; skip defensively
     }
-    if (len + 1 > c.MW || len + 1 > MAXW) {
-      if (len + 1 > c.MW) {
-        continue;  // over the slab matrix: host drops these (defensive)
-      }
-      c.status = kPoaWidthOverflow;  // mis-bucketed: fail to the CPU path
+    if (len + 1 > MAXW) {
+      c.status = kPoaWidthOverflow;  // mis-routed: fail to the CPU path
       break;
     }
 
-    // build the per-layer match bitvectors straight from the (L2-resident)
-    // global layer bytes, lane-parallel over chunk words; one spare zero
-    // word so cross-word extraction never reads out of bounds
-    {
-      const uint32_t words = (len + kLanes - 1) / kLanes + 1;
-      for (uint32_t w = lane; w < words * 4; w += kLanes) {
-        const uint32_t k = w >> 2, cc = w & 3;
-        uint64_t bits = 0;
-        const uint32_t base = k * kLanes;
-        if (base < len) {
-          const uint32_t lim = min(kLanes, len - base);
-          for (uint32_t l = 0; l < lim; ++l) {
-            if (poa_code(seq[base + l]) == static_cast<int32_t>(cc)) {
-              bits |= 1ull << l;
-            }
-          }
-        }
-        s.match[cc][k] = bits;
-      }
-    }
-    __syncthreads();
+    build_match_bits_d(s, seq, len, lane);
 
     const uint32_t n = c.num_nodes;
-    const uint32_t chunks = (len + kLanes - 1) / kLanes;
-
-    // SUBGRAPH restriction (CPU parity, Window::generate_consensus): a
-    // layer that does not span the window aligns only against the rank
-    // window [rank(backbone[begin]), rank(backbone[end])]. Rows outside are
-    // skipped, predecessor edges from below rank(begin) are ignored (rows
-    // losing every predecessor become NW start rows), and the alignment
-    // target is the span's end rank (plus true sinks inside the window).
-    // The reference's cudapoa aligns every layer to the full graph instead,
-    // which is what degrades its long-window GPU goldens (racon_test.cpp
-    // pins 4168 vs CPU 1289 at w=1000); this engine keeps the CPU
-    // windowing semantics on device.
+    LayerDp d;
+    d.seq = seq;
+    d.len = len;
+    d.chunks = (len + kLanes - 1) / kLanes;
     const uint32_t span_word = c.spans[layer];
-    const bool sub = span_word != 0xFFFFFFFFu;
-    uint32_t rlo = 0, rhi = n - 1;
-    if (sub) {
-      rlo = c.rank[span_word >> 16];
-      rhi = c.rank[span_word & 0xffffu];
-    }
-
-    // banded mode (-b): static band around the rank diagonal of the
-    // (possibly rank-restricted) row window
-    const bool banded = (c.bw != 0) && (c.bw < len);
-    const uint32_t slope16 =
-        banded ? static_cast<uint32_t>((static_cast<uint64_t>(len) << 16) / (rhi - rlo + 1))
-               : 0;
+    d.sub = span_word != 0xFFFFFFFFu;
+    d.rlo = d.sub ? c.rank[span_word >> 16] : 0;
+    d.rhi = d.sub ? c.rank[span_word & 0xffffu] : n - 1;
+    d.bw = a.band_width;
+    d.banded = (d.bw != 0) && (d.bw < len);
+    d.slope16 = d.banded ? static_cast<uint32_t>((static_cast<uint64_t>(len) << 16) /
+                                                 (d.rhi - d.rlo + 1))
+                         : 0;
 
     int32_t best_score = kNegInf;
     uint32_t best_row = 0;
     (void)lap();
 
-    // row 0 (all-gap) is arithmetic: H0[j] = j * g — never materialized.
     // Row descriptors are staged 64 at a time through LDS with one
     // coalesced load: a per-row dependent global read (~600 ns) was the
     // dominant per-row latency and neither scan nor store restructuring
     // moved it (measured via RGA_POA_TIMING).
-    for (uint32_t rblk = rlo & ~(kLanes - 1); rblk <= rhi; rblk += kLanes) {
+    for (uint32_t rblk = d.rlo & ~(kLanes - 1); rblk <= d.rhi; rblk += kLanes) {
       if (rblk + lane < n) {
         s.rd_block[lane] = c.row_desc[rblk + lane];
       }
       wave_lds_sync();
-      const uint32_t rlim = min(rhi + 1, rblk + kLanes);
-    for (uint32_t r = max(rblk, rlo); r < rlim; ++r) {
-      const uint64_t rd = s.rd_block[r - rblk];
-      const uint8_t letter = static_cast<uint8_t>(rd);
-      const int32_t letter_code = poa_code(letter);
-      const uint32_t nin = static_cast<uint32_t>((rd >> 8) & 0xff);
-      const uint32_t node = static_cast<uint32_t>((rd >> 16) & 0xffff);
-      const uint32_t pred0 = static_cast<uint32_t>((rd >> 32) & 0xffff);
-      const uint64_t flags = (rd >> 48) & 0xff;
-      const bool is_end = (flags & kRdEnd) != 0;
-      const bool store_row = (flags & kRdStore) != 0;
-      int16_t* Hrow = c.matrix + static_cast<size_t>(r + 1) * c.MW;
-      uint8_t* Mrow = c.moves + static_cast<size_t>(r + 1) * c.MW;
-      int16_t* ring_row = s.u.ring[(r + 1) % kRing];
-
-      // predecessor rows (e < kMaxPre precomputed; beyond that re-derived
-      // in the chunk loop — nodes with >8 in-edges are rare)
-      uint32_t pred_rows[kMaxPre];
-      pred_rows[0] = pred0;
-      const uint32_t npre = min(nin, kMaxPre);
-      for (uint32_t e = 1; e < npre; ++e) {
-        pred_rows[e] = c.rank[c.in_edges[node * c.ME + e]] + 1;
+      const uint32_t rlim = min(d.rhi + 1, rblk + kLanes);
+      for (uint32_t r = max(rblk, d.rlo); r < rlim; ++r) {
+        dp_row<WB, MAXW>(c, s, d, r, s.rd_block[r - rblk], lane, best_score, best_row);
       }
-
-      // usable predecessor edges: in subgraph mode edges from ranks below
-      // the window are cut; a row losing every predecessor becomes an NW
-      // start row (virtual row 0), matching the CPU subgraph's sources.
-      // Edge index 63 in a move byte encodes that virtual start for the
-      // traceback (real indices stop at max_edges-1 = 47).
-      uint64_t usable = (1ull << nin) - 1;  // nin <= 48 < 64
-      if (sub && nin != 0) {
-        usable = 0;
-        for (uint32_t e = 0; e < nin; ++e) {
-          const uint32_t p = (e < kMaxPre) ? pred_rows[e]
-                                           : c.rank[c.in_edges[node * c.ME + e]] + 1;
-          if (p > rlo) {
-            usable |= 1ull << e;
-          }
-        }
-      }
-      const bool vstart = usable == 0;  // nin == 0, or every pred cut
-
-      uint32_t row_klo = 0, row_khi = chunks - 1;
-      if (banded) {
-        band_chunks(r + 1 - rlo, slope16, c.bw, chunks, &row_klo, &row_khi);
-      }
-
-      // fetch a predecessor row value: LDS ring if close, global otherwise;
-      // in banded mode, columns outside the predecessor's band are -inf
-      auto pred_val = [&](uint32_t p, uint32_t col) -> int32_t {
-        if (p == 0) {
-          return static_cast<int32_t>(col) * c.g;  // arithmetic row 0
-        }
-        if (banded && col != 0) {
-          uint32_t pklo, pkhi;
-          band_chunks(p - rlo, slope16, c.bw, chunks, &pklo, &pkhi);
-          const uint32_t kc = (col - 1) / 64;
-          if (kc < pklo || kc > pkhi) {
-            return kNegInf;
-          }
-        } else if (banded && col == 0) {
-          uint32_t pklo, pkhi;
-          band_chunks(p - rlo, slope16, c.bw, chunks, &pklo, &pkhi);
-          if (pklo != 0) {
-            return kNegInf;
-          }
-        }
-        if (r + 1 - p < kRing) {
-          return s.u.ring[p % kRing][col];
-        }
-        return c.matrix[static_cast<size_t>(p) * c.MW + col];
-      };
-
-      // first column (j = 0): max over preds of Hp[0] + gap
-      // (banded: only when this row's band includes column 0)
-      int32_t h0 = kNegInf;
-      uint32_t e0 = 0;
-      if (row_klo == 0) {
-        int32_t best0 = kNegInf;
-        if (vstart) {
-          best0 = 0;
-          e0 = 63;  // virtual-start sentinel (see `usable`)
-        } else {
-          for (uint32_t e = 0; e < nin; ++e) {
-            if (!((usable >> e) & 1)) {
-              continue;
-            }
-            const uint32_t p = (e < kMaxPre) ? pred_rows[e]
-                                             : c.rank[c.in_edges[node * c.ME + e]] + 1;
-            const int32_t hp0 = pred_val(p, 0);
-            if (hp0 > best0) {
-              best0 = hp0;
-              e0 = e;
-            }
-          }
-        }
-        h0 = best0 + c.g;
-        if (lane == 0) {
-          if (store_row) {
-            Hrow[0] = static_cast<int16_t>(h0);
-          }
-          ring_row[0] = static_cast<int16_t>(h0);
-          // column 0 is always a vertical chain through the argmax edge
-          // (moves layout is shifted: col j lives at j-1, col 0 at MW-1,
-          // so each lane's 8 move bytes form one aligned u64 store)
-          Mrow[c.MW - 1] = static_cast<uint8_t>(kMvUp | (e0 << 2));
-        }
-      }
-
-      // ---- lane-blocked columns ----
-      // Lane l owns WB contiguous columns per pass; one register-local
-      // inclusive scan + one DPP wave scan per pass replaces the previous
-      // chunk-serial carry chain (8 dependent LDS+scan segments per row).
-      const uint32_t j0 = banded ? row_klo * kLanes : 0;
-      const uint32_t jend = banded ? min(len, (row_khi + 1) * kLanes) : len;
-      int32_t carry_u = h0;  // u-space max through column j0 (h0 = -inf when
-                             // the band excludes column 0)
-      int32_t last_col_val = kNegInf;
-      int32_t pass_tail = 0;  // lane 63's last clamped value of the previous
-                              // pass (the shifted store's column `base`)
-
-      for (uint32_t base = j0; base < jend; base += kLanes * WB) {
-        const uint32_t cbase = base + lane * WB;  // own cols: cbase+1..cbase+WB
-        const uint32_t nown =
-            (cbase < jend) ? min(WB, jend - cbase) : 0;
-
-        // substitution matches for own columns: bits w of mbits
-        uint64_t mbits = 0;
-        if (letter_code >= 0 && nown > 0) {
-          const uint32_t bit0 = cbase & 63;
-          const uint32_t w0 = cbase >> 6;
-          mbits = s.match[letter_code][w0] >> bit0;
-          if (bit0 != 0) {
-            mbits |= s.match[letter_code][w0 + 1] << (64 - bit0);
-          }
-        } else if (nown > 0) {
-          for (uint32_t w = 0; w < nown; ++w) {
-            if (seq[cbase + w] == letter) {  // rare: non-ACGT row letter
-              mbits |= 1ull << w;
-            }
-          }
-        }
-
-        int32_t bd[WB], bu[WB];  // best diagonal / vertical candidates
-#pragma unroll
-        for (uint32_t w = 0; w < WB; ++w) {
-          bd[w] = kNegInf;
-          bu[w] = kNegInf;
-        }
-
-        if (vstart) {
-#pragma unroll
-          for (uint32_t w = 0; w < WB; ++w) {
-            if (w < nown) {
-              const int32_t j = static_cast<int32_t>(cbase + 1 + w);
-              const int32_t subst = ((mbits >> w) & 1) ? c.m : c.x;
-              bd[w] = (j - 1) * c.g + subst;
-              bu[w] = j * c.g + c.g;
-            }
-          }
-        } else {
-          for (uint32_t e = 0; e < nin; ++e) {
-            if (!((usable >> e) & 1)) {
-              continue;
-            }
-            const uint32_t p = (e < kMaxPre) ? pred_rows[e]
-                                             : c.rank[c.in_edges[node * c.ME + e]] + 1;
-            // gather pred row values pv[w] = H(p, cbase + w), w in 0..WB.
-            // Loads are UNCONDITIONAL with a clamped index + VALU select:
-            // per-element predication compiled to one exec-branched
-            // flat_load each (generic pointer), serializing the row. The
-            // LDS and global paths are separate loops so each keeps its
-            // address space (ds_read vs global_load).
-            int32_t pv[WB + 1];
-            if (p == 0) {
-#pragma unroll
-              for (uint32_t w = 0; w <= WB; ++w) {
-                pv[w] = static_cast<int32_t>(cbase + w) * c.g;
-              }
-            } else {
-              uint32_t plo = 0, phi = len;  // valid column range of pred row
-              bool p_has0 = true;
-              if (banded) {
-                uint32_t pklo, pkhi;
-                band_chunks(p - rlo, slope16, c.bw, chunks, &pklo, &pkhi);
-                plo = pklo * kLanes;  // valid cols: {0 if pklo==0} + [plo+1..phi]
-                phi = min(len, (pkhi + 1) * kLanes);
-                p_has0 = (pklo == 0);
-              }
-              // validity of the contiguous range [plo+1, phi] (plus col 0
-              // when the pred row computed it) hoisted into ONE bitmask per
-              // edge — per-element compare+select chains were ~10% of the
-              // kernel's VALU issue
-              const uint32_t lo_col = plo + 1;
-              const uint32_t lo_w = lo_col > cbase ? min(lo_col - cbase, WB + 1) : 0;
-              const uint32_t hi_w = (phi + 1 > cbase) ? min(phi + 1 - cbase, WB + 1) : 0;
-              uint32_t okmask = (hi_w > lo_w) ? ((1u << hi_w) - (1u << lo_w)) : 0u;
-              if (cbase == 0 && p_has0) {
-                okmask |= 1u;  // col 0 sits outside [plo+1, phi] by construction
-              }
-              const uint32_t colmax = c.MW - 1;
-              constexpr uint32_t kRingMax = MAXW - 1;  // LDS ring row bound
-              // unpack a 16-byte vector load into pv[0..7] (cbase*2 is a
-              // multiple of 16 when WB == 8, and both the ring rows and the
-              // global matrix rows are 16-byte aligned); replaces 8 scalar
-              // b16 loads — the LDS pipe is the congested unit at 20+
-              // co-resident windows per CU (profiles/PARKED.md)
-              auto unpack8 = [&pv](int4 v) {
-                const int32_t ws[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-                for (uint32_t q = 0; q < 4; ++q) {
-                  pv[2 * q] = static_cast<int32_t>(static_cast<int16_t>(ws[q] & 0xffff));
-                  pv[2 * q + 1] = ws[q] >> 16;  // arithmetic: sign-extended
-                }
-              };
-              if (r + 1 - p < kRing) {
-                const uint32_t slot = p % kRing;
-                if (WB == 8 && cbase + WB <= kRingMax) {
-                  unpack8(*reinterpret_cast<const int4*>(&s.u.ring[slot][cbase]));
-                  pv[WB] = s.u.ring[slot][cbase + WB];
-#pragma unroll
-                  for (uint32_t w = 0; w <= WB; ++w) {
-                    pv[w] = ((okmask >> w) & 1u) ? pv[w] : kNegInf;
-                  }
-                } else if (cbase + WB <= kRingMax) {
-#pragma unroll
-                  for (uint32_t w = 0; w <= WB; ++w) {
-                    const int32_t val = s.u.ring[slot][cbase + w];
-                    pv[w] = ((okmask >> w) & 1u) ? val : kNegInf;
-                  }
-                } else {
-#pragma unroll
-                  for (uint32_t w = 0; w <= WB; ++w) {
-                    const int32_t val = s.u.ring[slot][min(cbase + w, kRingMax)];
-                    pv[w] = ((okmask >> w) & 1u) ? val : kNegInf;
-                  }
-                }
-              } else {
-                const int16_t* gsrc = c.matrix + static_cast<size_t>(p) * c.MW;
-                if (WB == 8 && cbase + WB <= colmax) {
-                  unpack8(*reinterpret_cast<const int4*>(gsrc + cbase));
-                  pv[WB] = gsrc[cbase + WB];
-#pragma unroll
-                  for (uint32_t w = 0; w <= WB; ++w) {
-                    pv[w] = ((okmask >> w) & 1u) ? pv[w] : kNegInf;
-                  }
-                } else if (cbase + WB <= colmax) {
-#pragma unroll
-                  for (uint32_t w = 0; w <= WB; ++w) {
-                    const int32_t val = gsrc[cbase + w];
-                    pv[w] = ((okmask >> w) & 1u) ? val : kNegInf;
-                  }
-                } else {
-#pragma unroll
-                  for (uint32_t w = 0; w <= WB; ++w) {
-                    const int32_t val = gsrc[min(cbase + w, colmax)];
-                    pv[w] = ((okmask >> w) & 1u) ? val : kNegInf;
-                  }
-                }
-              }
-            }
-            // no nown guard: out-of-range pv entries are -inf and propagate
-#pragma unroll
-            for (uint32_t w = 0; w < WB; ++w) {
-              const int32_t sub = ((mbits >> w) & 1) ? c.m : c.x;
-              bd[w] = max(bd[w], pv[w] + sub);
-              bu[w] = max(bu[w], pv[w + 1] + c.g);
-            }
-          }
-        }
-
-        // local inclusive u-space scan over own columns (out-of-range
-        // candidates are already -inf; no per-element guard needed)
-        int32_t us[WB];
-        int32_t run = kNegInf;
-#pragma unroll
-        for (uint32_t w = 0; w < WB; ++w) {
-          const int32_t j = static_cast<int32_t>(cbase + 1 + w);
-          const int32_t u = max(bd[w], bu[w]) - j * c.g;
-          run = max(run, u);
-          us[w] = run;
-        }
-        // wave scan over lane totals -> exclusive prefix for this lane
-        const int32_t incl = wave_scan_max(run, lane);
-        int32_t excl =
-            __builtin_amdgcn_update_dpp(kNegInf, incl, 0x138, 0xf, 0xf, false);  // wave_shr:1
-        excl = max(excl, carry_u);
-        // next pass's carry: wave-uniform max over everything <= this pass
-        carry_u = max(carry_u, __builtin_amdgcn_readlane(incl, kLanes - 1));
-
-        // finalize own columns: h, moves, stores. h is computed for every
-        // slot (junk past the row end feeds only junk columns); the move
-        // logic stays guarded.
-        int32_t h_sel = kNegInf;
-        uint64_t mvpack = 0;  // 8 move bytes -> one aligned store at Mrow[cbase]
-        int32_t harr[WB];
-#pragma unroll
-        for (uint32_t w = 0; w < WB; ++w) {
-          const uint32_t j = cbase + 1 + w;
-          const int32_t v = max(bd[w], bu[w]);
-          const int32_t h = max(us[w], excl) + static_cast<int32_t>(j) * c.g;
-          harr[w] = h < -28000 ? -28000 : h;
-          if (w < nown) {
-            uint8_t mv;
-            if (h != v) {
-              mv = kMvLeft;
-            } else if (vstart) {
-              mv = static_cast<uint8_t>(((bd[w] >= bu[w]) ? kMvDiag : kMvUp) | (63u << 2));
-            } else if (nin == 1) {
-              mv = (bd[w] >= bu[w]) ? kMvDiag : kMvUp;
-            } else {
-              // rare multi-pred row: recover the argmax edge (first e wins)
-              const uint8_t type = (bd[w] >= bu[w]) ? kMvDiag : kMvUp;
-              const int32_t want = (type == kMvDiag) ? bd[w] : bu[w];
-              uint32_t esel = 0;
-              const int32_t sub = ((mbits >> w) & 1) ? c.m : c.x;
-              for (uint32_t e = 0; e < nin; ++e) {
-                if (!((usable >> e) & 1)) {
-                  continue;
-                }
-                const uint32_t p = (e < kMaxPre)
-                                       ? pred_rows[e]
-                                       : c.rank[c.in_edges[node * c.ME + e]] + 1;
-                const int32_t cand =
-                    (type == kMvDiag) ? pred_val(p, j - 1) + sub : pred_val(p, j) + c.g;
-                if (cand == want) {
-                  esel = e;
-                  break;
-                }
-              }
-              mv = static_cast<uint8_t>(type | (esel << 2));
-            }
-            if (WB == 8) {
-              mvpack |= static_cast<uint64_t>(mv) << (8 * w);
-              if (a.vstore_mode != 1) {
-                if (store_row) {
-                  Hrow[j] = static_cast<int16_t>(harr[w]);
-                }
-                ring_row[j] = static_cast<int16_t>(harr[w]);
-              }
-            } else {
-              if (store_row) {
-                Hrow[j] = static_cast<int16_t>(harr[w]);
-              }
-              ring_row[j] = static_cast<int16_t>(harr[w]);
-              Mrow[j - 1] = mv;  // shifted layout, per-byte for odd widths
-            }
-            if (j == len) {
-              h_sel = h;
-            }
-          }
-        }
-        if (WB == 8 && a.vstore_mode != 0) {
-          // Shifted 16-byte row stores: lane l writes columns
-          // [cbase .. cbase+7] = [neighbor's last value | own h[0..6]] so
-          // the store is one aligned b128 instead of 8 b16 ops (LDS-pipe
-          // congestion is the bottleneck — profiles/PARKED.md). Column
-          // `base` comes from lane 63 of the previous pass (or h0), the
-          // pass-boundary column base+512 from the NEXT pass's lane 0, and
-          // a row ending exactly on the boundary stores it explicitly.
-          const int32_t tail_in = (base == j0) ? h0 : pass_tail;
-          const int32_t shifted =
-              __builtin_amdgcn_update_dpp(tail_in, harr[WB - 1], 0x138, 0xf, 0xf, false);
-          pass_tail = __builtin_amdgcn_readlane(harr[WB - 1], kLanes - 1);
-          if (cbase < jend) {
-            int4 vec;
-            vec.x = (shifted & 0xffff) | (harr[0] << 16);
-            vec.y = (harr[1] & 0xffff) | (harr[2] << 16);
-            vec.z = (harr[3] & 0xffff) | (harr[4] << 16);
-            vec.w = (harr[5] & 0xffff) | (harr[6] << 16);
-            *reinterpret_cast<int4*>(&ring_row[cbase]) = vec;
-            if (store_row) {
-              *reinterpret_cast<int4*>(Hrow + cbase) = vec;
-            }
-          }
-          // When this pass's last covered column is `len` itself AND len
-          // lands on a lane boundary ((len - base) % WB == 0), the lane
-          // that would store it via its shifted slot has cbase == len and
-          // is excluded by the cbase < jend guard — store it explicitly
-          // from the owning lane's last value. (Missing this for ANY
-          // multiple-of-8 row length left ring[len] uninitialized and made
-          // results depend on stale LDS — caught by tools/probe_order.py.)
-          const uint32_t rem = len > base ? len - base : 0;
-          if (rem > 0 && rem <= kLanes * WB && (rem & (WB - 1)) == 0) {
-            const int owner = static_cast<int>(rem / WB) - 1;
-            const int32_t t16 = __builtin_amdgcn_readlane(harr[WB - 1], owner);
-            if (lane == 0) {
-              ring_row[len] = static_cast<int16_t>(t16);
-              if (store_row) {
-                Hrow[len] = static_cast<int16_t>(t16);
-              }
-            }
-          }
-        }
-        if (WB == 8 && cbase < len) {
-          if (cbase + WB < c.MW) {
-            // one aligned u64 store covers the lane's 8 move bytes
-            // (cbase is a multiple of 8 exactly when WB == 8); bytes beyond
-            // nown encode columns past the row end and are never read back
-            *reinterpret_cast<uint64_t*>(Mrow + cbase) = mvpack;
-          } else {
-            // near-full row: byte MW-1 is the shifted column-0 slot (stored
-            // above as kMvUp); a packed store here would clobber it with the
-            // padding byte 0 (kMvDiag) and derail the traceback at j==0.
-            // Store only the live bytes individually.
-            for (uint32_t w = 0; w < nown; ++w) {
-              Mrow[cbase + w] = static_cast<uint8_t>(mvpack >> (8 * w));
-            }
-          }
-        }
-        if (len > base && len <= base + kLanes * WB) {
-          const int owner = static_cast<int>((len - 1 - base) / WB);
-          const int32_t lc = __builtin_amdgcn_readlane(h_sel, owner);
-          last_col_val = lc;
-        }
-      }
-
-      // ring writes must be visible to every lane before the next row;
-      // deliberately NOT __syncthreads (would drain the global row stores)
-      wave_lds_sync();
-
-      // end-node max (strict >, first in topological order wins);
-      // last_col_val is already wave-uniform (readlane). In subgraph mode
-      // the span's end rank is the alignment sink (plus true sinks inside
-      // the window).
-      if ((is_end || (sub && r == rhi)) && last_col_val > best_score) {
-        best_score = last_col_val;
-        best_row = r + 1;
-      }
-    }
       wave_lds_sync();  // rows done before the next cooperative rd_block load
     }
 
@@ -1161,55 +1187,7 @@ __global__ void poa_window_kernel(PoaDeviceArena a, uint32_t window_base,
 
     // ---- serial phases on lane 0 ----
     if (lane == 0) {
-      // move-byte traceback
-      int32_t aln_len = 0;
-      uint32_t i = best_row, j = len;
-      while (!(i == 0 && j == 0)) {
-        uint32_t prev_i = i, prev_j = j;
-        int32_t rec_node = -1, rec_seq = -1;
-        if (i == 0) {
-          // row 0: all-gap prefix — consume remaining columns
-          rec_seq = static_cast<int32_t>(j - 1);
-          prev_j = j - 1;
-        } else {
-          const uint8_t mv =
-              c.moves[static_cast<size_t>(i) * c.MW + (j != 0 ? j - 1 : c.MW - 1)];
-          const uint8_t type = mv & 3;
-          const uint32_t e = mv >> 2;
-          const uint64_t rd = c.row_desc[i - 1];
-          const uint32_t node = static_cast<uint32_t>((rd >> 16) & 0xffff);
-          const uint32_t nin = static_cast<uint32_t>((rd >> 8) & 0xff);
-          if (type == kMvLeft) {
-            rec_seq = static_cast<int32_t>(j - 1);
-            prev_j = j - 1;
-          } else {
-            uint32_t p = 0;  // virtual row 0: genuine start rows (nin==0)
-                             // and subgraph sources (edge sentinel 63)
-            if (nin != 0 && e != 63) {
-              p = (e == 0) ? static_cast<uint32_t>((rd >> 32) & 0xffff)
-                           : c.rank[c.in_edges[node * c.ME + e]] + 1;
-            }
-            if (type == kMvDiag) {
-              rec_node = static_cast<int32_t>(node);
-              rec_seq = static_cast<int32_t>(j - 1);
-              prev_i = p;
-              prev_j = j - 1;
-            } else if (type == kMvUp) {
-              rec_node = static_cast<int32_t>(node);
-              prev_i = p;
-            } else {
-              c.status = kPoaConsensusOverflow;  // invalid move: fail window
-              break;
-            }
-          }
-        }
-        c.aln_nodes[aln_len] = rec_node;
-        c.aln_seq[aln_len] = rec_seq;
-        ++aln_len;
-        i = prev_i;
-        j = prev_j;
-      }
-
+      const int32_t aln_len = traceback_d(c, best_row, len);
       t_tb += lap();
       if (c.status == kPoaOk) {
         add_alignment_d(c, seq, wts, len, aln_len);
@@ -1243,12 +1221,12 @@ __global__ void poa_window_kernel(PoaDeviceArena a, uint32_t window_base,
 
   // ---- consensus ----
   if (lane == 0) {
-    uint8_t* out = a.consensus + static_cast<size_t>(win) * L.max_consensus;
-    uint16_t* cov = a.coverage + static_cast<size_t>(win) * L.max_consensus;
+    uint8_t* out = a.consensus + static_cast<size_t>(win) * kPoaLimits.max_consensus;
+    uint16_t* cov = a.coverage + static_cast<size_t>(win) * kPoaLimits.max_consensus;
     int32_t clen = -1;
     (void)lap();
     if (c.status == kPoaOk) {
-      clen = consensus_d(c, s, out, cov, L.max_consensus);
+      clen = consensus_d(c, s, out, cov, kPoaLimits.max_consensus);
     }
     t_cons = lap();
     a.consensus_len[win] = clen < 0 ? 0 : static_cast<uint32_t>(clen);
@@ -1266,66 +1244,52 @@ __global__ void poa_window_kernel(PoaDeviceArena a, uint32_t window_base,
   }
 }
 
+// One launch per table row: separate __global__ instantiations per
+// (columns-per-lane, ring-width) variant, because one kernel containing all
+// variants pays the widest variant's registers and LDS on every path
+// (measured 3x occupancy collapse).
+// Measured: the power-of-two 8-wide variant (two passes for a 530-column
+// window) beats a 9-wide single-pass variant by ~8% — non-power-of-two
+// unrolls lose more in generated address code than the extra, mostly
+// empty pass costs. The ring width (LDS) sets occupancy; see Shared<W>.
+template <bool TIMED, PoaVariant V>
+void launch_variant(const PoaDeviceArena& arena, uint32_t window_base, uint32_t num_windows,
+                    hipStream_t stream) {
+  constexpr PoaVariantParams p = kPoaVariants[V];
+  hipLaunchKernelGGL(
+      (poa_window_kernel<TIMED, p.cols_per_lane, p.ring_width, p.node_cap, p.min_waves>),
+      dim3(num_windows), dim3(kLanes), 0, stream, arena, window_base, num_windows);
+}
+
+template <bool TIMED>
+void dispatch_variant(const PoaDeviceArena& arena, uint32_t window_base, uint32_t num_windows,
+                      PoaVariant variant, hipStream_t stream) {
+  switch (variant) {
+    case kPoaNarrow:
+      return launch_variant<TIMED, kPoaNarrow>(arena, window_base, num_windows, stream);
+    case kPoaMid:
+      return launch_variant<TIMED, kPoaMid>(arena, window_base, num_windows, stream);
+    case kPoaFull:
+      return launch_variant<TIMED, kPoaFull>(arena, window_base, num_windows, stream);
+    case kPoaBandedMid:
+      return launch_variant<TIMED, kPoaBandedMid>(arena, window_base, num_windows, stream);
+    case kPoaBandedFull:
+      return launch_variant<TIMED, kPoaBandedFull>(arena, window_base, num_windows, stream);
+    case kPoaNumVariants:
+      break;
+  }
+}
+
 }  // namespace
 
 void launch_poa_kernel(const PoaDeviceArena& arena, uint32_t window_base,
-                       uint32_t num_windows, uint32_t bucket, void* stream) {
+                       uint32_t num_windows, PoaVariant variant, void* stream) {
   static const bool timed = getenv("RGA_POA_TIMING") != nullptr;
   auto st = static_cast<hipStream_t>(stream);
-  const dim3 grid(num_windows), block(kLanes);
-  // separate __global__ instantiations per (columns-per-lane, ring-width)
-  // bucket: one kernel containing all variants pays the widest variant's
-  // registers and LDS on every path (measured 3x occupancy collapse).
-  // Measured: the power-of-two 8-wide variant (two passes for a 530-column
-  // window) beats a 9-wide single-pass variant by ~8% — non-power-of-two
-  // unrolls lose more in generated address code than the extra, mostly
-  // empty pass costs. The ring width (LDS) sets occupancy; see Shared<W>.
   if (timed) {
-    switch (bucket) {
-      case 0:
-        hipLaunchKernelGGL((poa_window_kernel<true, 5, 384>), grid, block, 0, st, arena,
-                           window_base, num_windows);
-        break;
-      case 1:
-        hipLaunchKernelGGL((poa_window_kernel<true, 8, 576, 1536, 5>), grid, block, 0, st,
-                           arena, window_base, num_windows);
-        break;
-      case 3:
-        hipLaunchKernelGGL((poa_window_kernel<true, 5, 576>), grid, block, 0, st, arena,
-                           window_base, num_windows);
-        break;
-      case 4:
-        hipLaunchKernelGGL((poa_window_kernel<true, 5, 1024>), grid, block, 0, st, arena,
-                           window_base, num_windows);
-        break;
-      default:
-        hipLaunchKernelGGL((poa_window_kernel<true, 8, 1024>), grid, block, 0, st, arena,
-                           window_base, num_windows);
-        break;
-    }
+    dispatch_variant<true>(arena, window_base, num_windows, variant, st);
   } else {
-    switch (bucket) {
-      case 0:
-        hipLaunchKernelGGL((poa_window_kernel<false, 5, 384>), grid, block, 0, st, arena,
-                           window_base, num_windows);
-        break;
-      case 1:
-        hipLaunchKernelGGL((poa_window_kernel<false, 8, 576, 1536, 5>), grid, block, 0, st,
-                           arena, window_base, num_windows);
-        break;
-      case 3:
-        hipLaunchKernelGGL((poa_window_kernel<false, 5, 576>), grid, block, 0, st, arena,
-                           window_base, num_windows);
-        break;
-      case 4:
-        hipLaunchKernelGGL((poa_window_kernel<false, 5, 1024>), grid, block, 0, st, arena,
-                           window_base, num_windows);
-        break;
-      default:
-        hipLaunchKernelGGL((poa_window_kernel<false, 8, 1024>), grid, block, 0, st, arena,
-                           window_base, num_windows);
-        break;
-    }
+    dispatch_variant<false>(arena, window_base, num_windows, variant, st);
   }
 }
 

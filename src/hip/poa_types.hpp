@@ -7,22 +7,25 @@
 // serial graph phases on lane 0 hidden by 16-32 co-resident windows per CU.
 #pragma once
 
+#include <cstddef>
 #include <cstdint>
+#include <initializer_list>
 
 namespace rga::hip {
 
 // Capacity model (per window). Windows exceeding any cap are rejected or
 // failed on device and fall back to the CPU path (reference contract:
-// cudapolisher.cpp:354-383).
+// cudapolisher.cpp:354-383). Compile-time on both sides: the kernel keeps
+// slab addressing in immediates instead of ~100 live SGPRs that were
+// spilling into v_readlane/writelane traffic in the DP row loop.
 struct PoaLimits {
-  uint32_t max_seq_len = 1023;    // bases per layer (incl. backbone)
-  uint32_t max_depth = 200;       // layers per window (MAX_DEPTH_PER_WINDOW)
   uint32_t max_nodes = 2047;      // POA graph nodes per window
   uint32_t max_edges = 48;        // in- or out-edges per node
   uint32_t max_ring = 4;          // aligned-ring partners per node
-  uint32_t matrix_width = 1024;   // DP row width (max_seq_len + 1)
+  uint32_t matrix_width = 1024;   // DP row width (longest layer + 1)
   uint32_t max_consensus = 2048;  // consensus output cap
 };
+inline constexpr PoaLimits kPoaLimits{};
 
 // Window status codes produced by the kernel.
 enum PoaStatus : int32_t {
@@ -35,15 +38,148 @@ enum PoaStatus : int32_t {
   kPoaWidthOverflow = 6,  // layer wider than the launched ring variant
 };
 
+// ---- kernel variants ----
+// The kernel is instantiated once per row of kPoaVariants (times timed /
+// untimed). The enum's numeric order is the order a batch's windows are
+// sorted and launched in.
+enum PoaVariant : uint32_t {
+  kPoaNarrow = 0,      // rows <= 320 columns, single 5-wide pass
+  kPoaMid = 1,         // the hot one: default w=500 windows of moderate depth
+  kPoaFull = 2,        // anything else at full width
+  kPoaBandedMid = 3,   // banded rows in a mid-width ring
+  kPoaBandedFull = 4,  // banded rows in a full-width ring
+  kPoaNumVariants
+};
+
+struct PoaVariantParams {
+  uint32_t cols_per_lane;  // columns a lane owns per pass
+  uint32_t ring_width;     // LDS DP-row ring width; rows need max_len + 1
+  uint32_t node_cap;       // LDS Kahn capacity; the graph holds node_cap - 1
+  uint32_t min_waves;      // waves/SIMD the compiler budgets registers for
+};
+
+inline constexpr PoaVariantParams kPoaVariants[kPoaNumVariants] = {
+    {5, 384, kPoaLimits.max_nodes + 1, 4},                      // kPoaNarrow
+    {8, 576, 1536, 5},                                          // kPoaMid
+    {8, kPoaLimits.matrix_width, kPoaLimits.max_nodes + 1, 4},  // kPoaFull
+    {5, 576, kPoaLimits.max_nodes + 1, 4},                      // kPoaBandedMid
+    {5, kPoaLimits.matrix_width, kPoaLimits.max_nodes + 1, 4},  // kPoaBandedFull
+};
+
+// Variant for a window whose longest layer has max_len bases. The LDS ring
+// is indexed by ABSOLUTE column, so its width follows the true longest row
+// (max_len); only the columns-per-pass choice follows the banded clamp.
+// 9-wide single-pass was tried and spills 44-64 B/lane of scratch, which is
+// catastrophically slow; 8-wide multi-pass covers any width, and the ring
+// width picks the smallest LDS footprint the rows fit in.
+constexpr PoaVariant poa_route(uint32_t max_len, uint32_t num_seqs, uint32_t band_width) {
+  uint32_t pass_w = max_len;
+  if (band_width != 0 && band_width + 64 < pass_w) {
+    pass_w = band_width + 64;
+  }
+  const bool narrow_pass = pass_w <= 320;
+  if (max_len <= 320) return kPoaNarrow;
+  if (max_len <= 575) {
+    if (narrow_pass) return kPoaBandedMid;
+    // deep windows can outgrow the smaller node cap; route them to the
+    // full variant instead of bouncing via the CPU
+    return num_seqs <= 96 ? kPoaMid : kPoaFull;
+  }
+  return narrow_pass ? kPoaBandedFull : kPoaFull;
+}
+
+static_assert(poa_route(320, 12, 0) == kPoaNarrow && poa_route(321, 12, 0) == kPoaMid);
+static_assert(poa_route(575, 12, 0) == kPoaMid && poa_route(576, 12, 0) == kPoaFull);
+static_assert(poa_route(500, 96, 0) == kPoaMid && poa_route(500, 97, 0) == kPoaFull);
+static_assert(poa_route(320, 12, 256) == kPoaNarrow && poa_route(321, 12, 256) == kPoaBandedMid);
+static_assert(poa_route(575, 97, 256) == kPoaBandedMid &&
+              poa_route(576, 12, 256) == kPoaBandedFull);
+
+// every window is routed to a ring its rows fit in (the condition the
+// kernel's kPoaWidthOverflow guards)
+constexpr bool poa_routes_fit() {
+  for (uint32_t len = 0; len < kPoaLimits.matrix_width; ++len) {
+    for (uint32_t num_seqs : {1u, 96u, 97u}) {
+      for (uint32_t bw : {0u, 256u}) {
+        if (len + 1 > kPoaVariants[poa_route(len, num_seqs, bw)].ring_width) return false;
+      }
+    }
+  }
+  return true;
+}
+static_assert(poa_routes_fit());
+
 // Per-window input descriptor (layers already sorted: backbone first, then
 // by window start position — the same order as the CPU path).
 struct PoaWindowDesc {
   uint32_t seq_offset;   // byte offset into the packed seq/weight arena
-  uint32_t num_seqs;     // layers shipped to the device (<= max_depth + 1)
+  uint32_t num_seqs;     // layers shipped to the device (<= max depth + 1)
   uint32_t scratch_idx;  // which device slab this window uses
-  uint32_t max_len;      // longest layer (columns) — selects the kernel's
-                         // columns-per-lane instantiation
+  uint32_t max_len;      // longest layer (columns) — with num_seqs, picks the
+                         // kernel variant (poa_route)
 };
+
+// ---- per-window scratch slabs ----
+// X(element type, name, elements per window), in allocation order; N is
+// max_nodes and L the capacity model. This is the one statement of the slab
+// layout: the pointer struct, the size estimate, the host carve and the
+// kernel's per-window pointers are all expansions of it.
+//   nseq      sequences touching the node (coverage)
+//   rank      node -> rank (Kahn scratch/queue and the topological order
+//             itself live in LDS)
+//   hb_*      heaviest-bundle running scores / predecessors
+//   aln_*     alignment node ids / sequence positions (traceback output)
+//   matrix    DP scores
+//   moves     DP move bytes: bits 0-1 {0=diag,1=up,2=left,3=invalid},
+//             bits 2-7 in-edge index of the chosen predecessor
+//   row_desc  per-rank packed row descriptor, built lane-parallel after each
+//             topo sort: letter(8) | nin(8) | node(16) | pred_row(16) | flags(8)
+#define RGA_POA_SLAB_ARRAYS(X)                   \
+  X(uint8_t, letters, N)                         \
+  X(uint8_t, in_cnt, N)                          \
+  X(uint8_t, out_cnt, N)                         \
+  X(uint8_t, ring_cnt, N)                        \
+  X(uint16_t, in_edges, N * L.max_edges)         \
+  X(int32_t, in_weights, N * L.max_edges)        \
+  X(uint16_t, out_edges, N * L.max_edges)        \
+  X(uint16_t, ring, N * L.max_ring)              \
+  X(uint16_t, nseq, N)                           \
+  X(uint16_t, rank, N)                           \
+  X(int64_t, hb_score, N)                        \
+  X(int32_t, hb_pred, N)                         \
+  X(int32_t, aln_nodes, 2 * L.matrix_width + N)  \
+  X(int32_t, aln_seq, 2 * L.matrix_width + N)    \
+  X(int16_t, matrix, (N + 1) * L.matrix_width)   \
+  X(uint8_t, moves, (N + 1) * L.matrix_width)    \
+  X(uint64_t, row_desc, N)
+
+struct PoaSlabs {
+#define RGA_X(T, name, count) T* name;
+  RGA_POA_SLAB_ARRAYS(RGA_X)
+#undef RGA_X
+};
+
+// calls f(pointer member, elements per window) for every slab array, in
+// allocation order
+template <class F>
+constexpr void for_each_poa_slab(PoaSlabs& s, F&& f) {
+  constexpr PoaLimits L = kPoaLimits;
+  constexpr size_t N = L.max_nodes;
+#define RGA_X(T, name, count) f(s.name, static_cast<size_t>(count));
+  RGA_POA_SLAB_ARRAYS(RGA_X)
+#undef RGA_X
+}
+
+constexpr size_t kPoaTimingSlots = 8;
+
+// device scratch bytes one window needs (unrounded; sizes the batch)
+constexpr size_t poa_slab_bytes() {
+  PoaSlabs s{};
+  size_t b = kPoaTimingSlots * sizeof(unsigned long long);
+  for_each_poa_slab(s, [&b](auto* p, size_t count) { b += count * sizeof(*p); });
+  return b;
+}
+static_assert(poa_slab_bytes() == 7184020, "slab layout changed: batch sizes move with it");
 
 // Device arena pointers (one allocation, carved into slabs).
 struct PoaDeviceArena {
@@ -63,55 +199,28 @@ struct PoaDeviceArena {
   const PoaWindowDesc* windows;
 
   // per-window graph slabs (device scratch, indexed by scratch_idx)
-  uint8_t* letters;      // [max_nodes]
-  uint8_t* in_cnt;       // [max_nodes]
-  uint8_t* out_cnt;      // [max_nodes]
-  uint8_t* ring_cnt;     // [max_nodes]
-  uint16_t* in_edges;    // [max_nodes * max_edges]
-  int32_t* in_weights;   // [max_nodes * max_edges]
-  uint16_t* out_edges;   // [max_nodes * max_edges]
-  uint16_t* ring;        // [max_nodes * max_ring]
-  uint16_t* nseq;        // [max_nodes] sequences touching node (coverage)
-  uint16_t* rank;        // [max_nodes] node -> rank (Kahn scratch/queue and
-                         // the topological order itself live in LDS)
-  int64_t* hb_score;     // [max_nodes] heaviest-bundle running scores
-  int32_t* hb_pred;      // [max_nodes]
-  int32_t* aln_nodes;    // [2 * matrix_width + max_nodes] alignment node ids
-  int32_t* aln_seq;      // [same] alignment sequence positions
-  int16_t* matrix;       // [(max_nodes + 1) * matrix_width] DP scores
-  uint8_t* moves;        // [(max_nodes + 1) * matrix_width] DP move bytes:
-                         // bits 0-1 {0=diag,1=up,2=left,3=invalid}, bits 2-7
-                         // in-edge index of the chosen predecessor
-  uint64_t* row_desc;    // [max_nodes] per-rank packed row descriptor, built
-                         // lane-parallel after each topo sort: letter(8) |
-                         // nin(8) | node(16) | pred_row(16) | is_end(8)
+  PoaSlabs slabs;
 
   // per-window phase timing (wall_clock64 deltas; slots: 0 DP rows,
   // 1 traceback, 2 add_alignment, 3 topo sort, 4 row_desc, 5 consensus,
   // 6 total, 7 layers processed) — aggregated by the host under
   // RGA_POA_TIMING for kernel-phase attribution
-  unsigned long long* timing;  // [8] per window
+  unsigned long long* timing;  // [kPoaTimingSlots] per window
 
   // outputs (D2H once per batch)
-  uint8_t* consensus;     // [max_consensus] per window, reversed on host
-  uint16_t* coverage;     // [max_consensus] per window
+  uint8_t* consensus;       // [max_consensus] per window, forward order
+  uint16_t* coverage;       // [max_consensus] per window
   uint32_t* consensus_len;  // [1] per window
   int32_t* status;          // [1] per window
 
   int8_t match, mismatch, gap;
-  uint32_t vstore_mode;  // debug: 0 per-element row stores, 1 vector, 2 both
   uint32_t band_width;  // 0 = full-width DP; else static band (reference -b:
                         // BatchConfig band 256, src/cuda/cudabatch.cpp:56-59)
-  PoaLimits limits;
 };
 
-// Launches one (columns-per-lane, LDS-ring-width) kernel variant for
-// windows [window_base, window_base + num_windows) of the (bucket-sorted)
-// desc array. bucket: 0 = WB5/384-wide (rows <= 320 columns, single pass),
-// 1 = WB8/576-wide/1536-node (<= 575 and depth <= 96), 2 = WB8/1024-wide,
-// 3 = WB5/576-wide (banded rows in a 576 matrix), 4 = WB5/1024-wide
-// (banded rows in a full-width matrix).
+// Launches the kernel variant for windows [window_base, window_base +
+// num_windows) of the (variant-sorted) desc array.
 void launch_poa_kernel(const PoaDeviceArena& arena, uint32_t window_base,
-                       uint32_t num_windows, uint32_t bucket, void* stream);
+                       uint32_t num_windows, PoaVariant variant, void* stream);
 
 }  // namespace rga::hip

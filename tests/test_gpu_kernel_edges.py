@@ -711,6 +711,50 @@ def test_poa_batch_composition(racon, main_batch):
     assert alone == [gpu[k] for k in pick]
 
 
+_TIMED_CHILD = """
+import json, sys
+sys.path.insert(0, sys.argv[1])
+import _racon
+plain, banded = json.load(open(sys.argv[2]))
+as_windows = lambda ws: [[tuple(layer) for layer in w] for w in ws]
+print(json.dumps([_racon.poa_windows_gpu(as_windows(plain)),
+                  _racon.poa_windows_gpu(as_windows(banded), banded=True)]))
+"""
+
+
+def test_poa_timed_instantiations(racon, tmp_path):
+    """RGA_POA_TIMING selects the five TIMED=true kernel instantiations, which
+    nothing else launches. One window per variant (narrow, mid, full by depth,
+    banded mid, banded full) in a fresh process with the variable set must
+    give exactly what this process gives without it, with every window ok."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    assert "RGA_POA_TIMING" not in os.environ  # read once per process
+    rng = random.Random(7000)
+    plain = [_mutated_window(rng, 300, 12), _mutated_window(rng, 500, 12),
+             _mutated_window(rng, 500, 96, (0.01, 0.005, 0.005))]
+    banded = [_mutated_window(rng, 500, 12), _mutated_window(rng, 700, 12)]
+    # test-input sanity: the windows land where the routing thresholds say
+    longest = [max(len(layer[0]) for layer in w) for w in plain + banded]
+    assert longest[0] <= 320 and all(321 <= n <= 575 for n in longest[1:4]) and longest[4] >= 576
+    assert len(plain[2]) == 97
+
+    want = [racon.poa_windows_gpu(plain), racon.poa_windows_gpu(banded, banded=True)]
+    args = tmp_path / "windows.json"
+    args.write_text(json.dumps([plain, banded]))
+    child = subprocess.run(
+        [sys.executable, "-c", _TIMED_CHILD, os.path.dirname(racon.__file__), str(args)],
+        env=dict(os.environ, RGA_POA_TIMING="1"), capture_output=True, text=True, timeout=120)
+    assert child.returncode == 0, child.stderr[-2000:]
+    got = [[tuple(r) for r in call] for call in json.loads(child.stdout)]
+    assert got == want
+    assert all(ok for call in got for _, ok in call), got
+    assert child.stderr.count("timing (wall ticks") == 2, child.stderr[-2000:]
+
+
 def test_pipeline_n_in_draft_and_reads(racon, sample, fasta_reader, tmp_path):
     """Drafts with N runs are ordinary input. Here the draft has a 30-base N
     run and every read carries an N, so Sequence::acgt_only is false on both
