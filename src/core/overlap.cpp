@@ -203,35 +203,43 @@ void Overlap::find_breaking_points(const std::vector<std::unique_ptr<Sequence>>&
 }
 
 void Overlap::find_breaking_points_from_cigar(uint32_t window_length) {
+  breaking_points_ =
+      breaking_points_from_cigar(cigar_, window_length, t_begin_, t_end_, q_span_begin());
+}
+
+std::vector<std::pair<uint32_t, uint32_t>> breaking_points_from_cigar(
+    const std::string& cigar, uint32_t window_length, uint32_t t_begin, uint32_t t_end,
+    uint32_t q_begin) {
+  std::vector<std::pair<uint32_t, uint32_t>> points;
   // window-end target positions covered by this overlap (ref overlap.cpp:229-235)
   std::vector<int32_t> window_ends;
-  for (uint32_t i = 0; i < t_end_; i += window_length) {
-    if (i > t_begin_) {
+  for (uint32_t i = 0; i < t_end; i += window_length) {
+    if (i > t_begin) {
       window_ends.emplace_back(static_cast<int32_t>(i) - 1);
     }
   }
-  window_ends.emplace_back(static_cast<int32_t>(t_end_) - 1);
+  window_ends.emplace_back(static_cast<int32_t>(t_end) - 1);
 
   uint32_t w = 0;
   bool found_first_match = false;
   std::pair<uint32_t, uint32_t> first_match = {0, 0}, last_match = {0, 0};
 
-  int32_t q_ptr = static_cast<int32_t>(strand_ ? (q_length_ - q_end_) : q_begin_) - 1;
-  int32_t t_ptr = static_cast<int32_t>(t_begin_) - 1;
+  int32_t q_ptr = static_cast<int32_t>(q_begin) - 1;
+  int32_t t_ptr = static_cast<int32_t>(t_begin) - 1;
 
   auto close_window = [&]() {
     if (found_first_match) {
-      breaking_points_.emplace_back(first_match);
-      breaking_points_.emplace_back(last_match);
+      points.emplace_back(first_match);
+      points.emplace_back(last_match);
     }
     found_first_match = false;
     ++w;
   };
 
-  for (size_t i = 0, j = 0; i < cigar_.size(); ++i) {
-    char op = cigar_[i];
+  for (size_t i = 0, j = 0; i < cigar.size(); ++i) {
+    char op = cigar[i];
     if (op == 'M' || op == '=' || op == 'X') {
-      uint32_t n = static_cast<uint32_t>(atoi(cigar_.c_str() + j));
+      uint32_t n = static_cast<uint32_t>(atoi(cigar.c_str() + j));
       j = i + 1;
       for (uint32_t k = 0; k < n; ++k) {
         ++q_ptr;
@@ -246,10 +254,10 @@ void Overlap::find_breaking_points_from_cigar(uint32_t window_length) {
         }
       }
     } else if (op == 'I') {
-      q_ptr += atoi(cigar_.c_str() + j);
+      q_ptr += atoi(cigar.c_str() + j);
       j = i + 1;
     } else if (op == 'D' || op == 'N') {
-      uint32_t n = static_cast<uint32_t>(atoi(cigar_.c_str() + j));
+      uint32_t n = static_cast<uint32_t>(atoi(cigar.c_str() + j));
       j = i + 1;
       for (uint32_t k = 0; k < n; ++k) {
         ++t_ptr;
@@ -261,6 +269,7 @@ void Overlap::find_breaking_points_from_cigar(uint32_t window_length) {
       j = i + 1;
     }
   }
+  return points;
 }
 
 }  // namespace rga

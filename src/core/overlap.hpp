@@ -30,6 +30,17 @@ struct SequenceIndex {
   std::vector<uint64_t> target_ids;  // file-order target ordinal -> global index
 };
 
+// Per-window breaking points of one alignment: walks `cigar` from target
+// position t_begin and query position q_begin (on the strand the aligner
+// consumed) against window_length slices of the target aligned to coordinate
+// 0, the last one ending at t_end - 1. Returns, for every slice holding at
+// least one match, (t, q) of its first match and (t + 1, q + 1) of its last.
+// This walk is the specification the GPU aligner's breaking-point mode is
+// tested against.
+std::vector<std::pair<uint32_t, uint32_t>> breaking_points_from_cigar(
+    const std::string& cigar, uint32_t window_length, uint32_t t_begin, uint32_t t_end,
+    uint32_t q_begin);
+
 class Overlap {
  public:
   // MHAP record fields.
@@ -77,6 +88,13 @@ class Overlap {
 
   // CIGAR walk only (used by both CPU and GPU alignment paths).
   void find_breaking_points_from_cigar(uint32_t window_length);
+
+  // Breaking points computed elsewhere (the GPU aligner emits them directly).
+  void set_breaking_points(std::vector<std::pair<uint32_t, uint32_t>> points) {
+    breaking_points_ = std::move(points);
+  }
+  // Query position the alignment starts at, on the strand the aligner consumes.
+  uint32_t q_span_begin() const { return strand_ ? (q_length_ - q_end_) : q_begin_; }
 
   // The (query, target) character spans this overlap aligns, on the strand the
   // aligner consumes (query already reverse-complemented when strand_ is set).

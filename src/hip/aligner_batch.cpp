@@ -72,7 +72,7 @@ void AlignerBatch::allocate_arenas(size_t mem_budget) {
     return off;
   };
   size_t o_seqs = 0, o_descs = 0, o_peq = 0, o_tb = 0, o_s = 0, o_path = 0, o_plen = 0,
-         o_status = 0, o_ed = 0, o_order = 0, o_waves = 0;
+         o_status = 0, o_ed = 0, o_order = 0, o_waves = 0, o_bp = 0;
   uint32_t max_waves = 0;
   for (;; pool /= 2) {
     seq_cap_ = std::max<size_t>(16u << 20, pool / 96);
@@ -80,8 +80,14 @@ void AlignerBatch::allocate_arenas(size_t mem_budget) {
     peq_cap_u64_ = seq_cap_ / 8;  // 4 codes per 64 bases = q_bytes/2 of u64s
                                   // is generous; /8 covers wave-max padding
     max_alignments_ = 65536;
+    // window records: an alignment needs t_len / window_length + 2 at most,
+    // ~31 for a 15 kbp overlap at 500. One per 64 sequence bytes plus two per
+    // alignment never binds before the sequence arena at window_length >= 64
+    // (t_len is part of the alignment's sequence bytes); narrower windows
+    // can fill the record arena first and the batch then flushes early.
+    bp_cap_ = seq_cap_ / 64 + 2 * static_cast<size_t>(max_alignments_);
 
-    const size_t fixed = 2 * seq_cap_ + peq_cap_u64_ * 8 +
+    const size_t fixed = 2 * seq_cap_ + peq_cap_u64_ * 8 + bp_cap_ * sizeof(AlnBpRecord) +
                          max_alignments_ * (sizeof(AlnDesc) + 16) + (2u << 20);
     const size_t state = pool > fixed ? pool - fixed : (16u << 20);
     tb_cap_u64_ = state / 20 * 16 / 8;  // 16/20 of state bytes as u64
@@ -103,6 +109,7 @@ void AlignerBatch::allocate_arenas(size_t mem_budget) {
     o_ed = carve(max_alignments_ * 4);
     o_order = carve(max_alignments_ * 4);
     o_waves = carve(max_waves * sizeof(AlnWaveDesc));
+    o_bp = carve(bp_cap_ * sizeof(AlnBpRecord));
 
     hipError_t err = hipMalloc(&d_pool_, total);
     if (err == hipSuccess) {
@@ -126,6 +133,7 @@ void AlignerBatch::allocate_arenas(size_t mem_budget) {
   RGA_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h_order_), max_alignments_ * 4));
   RGA_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h_waves_),
                             max_waves * sizeof(AlnWaveDesc)));
+  RGA_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h_bp_), bp_cap_ * sizeof(AlnBpRecord)));
   auto base = static_cast<uint8_t*>(d_pool_);
   arena_.seqs = base + o_seqs;
   arena_.descs = reinterpret_cast<AlnDesc*>(base + o_descs);
@@ -136,6 +144,8 @@ void AlignerBatch::allocate_arenas(size_t mem_budget) {
   arena_.path_len = reinterpret_cast<uint32_t*>(base + o_plen);
   arena_.status = reinterpret_cast<int32_t*>(base + o_status);
   arena_.edit_distance = reinterpret_cast<int32_t*>(base + o_ed);
+  arena_.bp = reinterpret_cast<AlnBpRecord*>(base + o_bp);
+  arena_.window_length = 0;
   d_order_ = reinterpret_cast<uint32_t*>(base + o_order);
   d_waves_ = reinterpret_cast<AlnWaveDesc*>(base + o_waves);
   arena_.order = d_order_;
@@ -154,7 +164,8 @@ void AlignerBatch::release_all() {
   for (void* p : {static_cast<void*>(h_seqs_), static_cast<void*>(h_descs_),
                   static_cast<void*>(h_path_), static_cast<void*>(h_path_len_),
                   static_cast<void*>(h_status_), static_cast<void*>(h_edit_),
-                  static_cast<void*>(h_order_), static_cast<void*>(h_waves_)}) {
+                  static_cast<void*>(h_order_), static_cast<void*>(h_waves_),
+                  static_cast<void*>(h_bp_)}) {
     if (p != nullptr) {
       (void)hipHostFree(p);
     }
@@ -165,9 +176,26 @@ void AlignerBatch::release_all() {
 }
 
 int32_t AlignerBatch::reserve_span(const char* q, uint32_t q_len, const char* t,
-                                   uint32_t t_len, bool scan_non_acgt) {
+                                   uint32_t t_len, bool scan_non_acgt, uint32_t window_length,
+                                   uint32_t t_origin, uint32_t q_origin) {
   if (q_len == 0 || t_len == 0 || q_len > limits_.max_len || t_len > limits_.max_len) {
     return -2;  // reference: exceeded_max_length -> CPU fallback
+  }
+  // window slices [k * window_length, (k + 1) * window_length) of the target
+  // that the span touches: one record each
+  size_t bp_need = 0;
+  if (window_length > 0) {
+    const uint64_t t_last = static_cast<uint64_t>(t_origin) + t_len - 1;
+    if (t_last >= kAlnBpNone || static_cast<uint64_t>(q_origin) + q_len >= kAlnBpNone) {
+      return -2;  // positions must stay below the 32-bit no-match marker
+    }
+    bp_need = static_cast<size_t>(t_last / window_length - t_origin / window_length + 1);
+    if (bp_need > bp_cap_) {
+      return -2;
+    }
+  }
+  if (!overlaps_.empty() && window_length != window_length_) {
+    return -1;  // one product per fill: the caller flushes first
   }
   const size_t bytes = static_cast<size_t>(q_len) + t_len;
   // per-lane share of the wave's tb region (the wave total is 64 of these,
@@ -178,7 +206,8 @@ int32_t AlignerBatch::reserve_span(const char* q, uint32_t q_len, const char* t,
   // queue/threads).
   const uint64_t tb_need = static_cast<uint64_t>(t_len + 1) * band_k_ * 2;
   if (overlaps_.size() >= max_alignments_ || seq_bytes_ + bytes > seq_cap_ ||
-      path_bytes_ + bytes > path_cap_ || tb_reserved_ + tb_need > tb_cap_u64_ / 2) {
+      path_bytes_ + bytes > path_cap_ || tb_reserved_ + tb_need > tb_cap_u64_ / 2 ||
+      bp_records_ + bp_need > bp_cap_) {
     return -1;
   }
   // The kernel's base_code() matches A/C/G/T only, while the CPU aligner
@@ -200,6 +229,12 @@ int32_t AlignerBatch::reserve_span(const char* q, uint32_t q_len, const char* t,
   d.path_offset = static_cast<uint32_t>(path_bytes_);
   path_bytes_ += bytes;
   tb_reserved_ += tb_need;
+  d.t_origin = t_origin;
+  d.q_origin = q_origin;
+  d.bp_offset = static_cast<uint32_t>(bp_records_);
+  d.bp_count = static_cast<uint32_t>(bp_need);
+  bp_records_ += bp_need;
+  window_length_ = window_length;
 
   const int32_t slot = static_cast<int32_t>(overlaps_.size());
   h_descs_[slot] = d;
@@ -210,7 +245,7 @@ int32_t AlignerBatch::reserve_span(const char* q, uint32_t q_len, const char* t,
 
 bool AlignerBatch::add_overlap(Overlap* overlap,
                                const std::vector<std::unique_ptr<Sequence>>& sequences,
-                               bool* never_fits) {
+                               bool* never_fits, uint32_t window_length) {
   *never_fits = false;
   auto q = overlap->query_span(sequences);
   auto t = overlap->target_span(sequences);
@@ -220,7 +255,16 @@ bool AlignerBatch::add_overlap(Overlap* overlap,
   // sequence; a pure-ACGT draft never looks at its reads)
   const bool scan = !sequences[overlap->t_id()]->acgt_only() &&
                     !sequences[overlap->q_id()]->acgt_only();
-  int32_t slot = reserve_span(q.first, q.second, t.first, t.second, scan);
+  // RGA_ALN_HOST_BP=1 keeps the path -> CIGAR -> host walk route (A/B timing
+  // and the route differ test): the overlap is reserved in path mode and
+  // align_and_emit walks its CIGAR
+  static const bool host_bp = [] {
+    const char* e = getenv("RGA_ALN_HOST_BP");
+    return e != nullptr && atol(e) == 1;
+  }();
+  int32_t slot = reserve_span(q.first, q.second, t.first, t.second, scan,
+                              host_bp ? 0 : window_length, overlap->t_begin(),
+                              overlap->q_span_begin());
   if (slot == -2) {
     *never_fits = true;
     return false;
@@ -270,6 +314,7 @@ void AlignerBatch::run() {
   // lands on the wall clock; 16-32/wave gives each CU interleavable waves
   // at the cost of idle lanes (which issue no extra instructions).
   const uint32_t K = band_k_;
+  const bool emit_path = window_length_ == 0;
   // Full 64-lane packing for big jobs; small jobs still under-fill waves so
   // every CU gets interleavable work. (The 32-lane middle tier predated the
   // back-to-back sub-launch pipeline; measured post-pipeline, 64 wins at
@@ -359,13 +404,20 @@ void AlignerBatch::run() {
     launch_arena.order = d_order_ + wave_begin * lanes;
     launch_arena.waves = d_waves_ + wave_desc_off;
     launch_arena.lanes_per_wave = lanes;
-    launch_aligner_kernel(launch_arena, launch_waves, launch_align, K, stream_);
+    launch_arena.window_length = window_length_;
+    launch_aligner_kernel(launch_arena, launch_waves, launch_align, K, emit_path, stream_);
     wave_begin += launch_waves;
     wave_desc_off += launch_waves;
   }
 
-  RGA_HIP_CHECK(hipMemcpyAsync(h_path_, arena_.path, path_bytes_, hipMemcpyDeviceToHost, s));
-  RGA_HIP_CHECK(hipMemcpyAsync(h_path_len_, arena_.path_len, na * 4, hipMemcpyDeviceToHost, s));
+  if (emit_path) {
+    RGA_HIP_CHECK(hipMemcpyAsync(h_path_, arena_.path, path_bytes_, hipMemcpyDeviceToHost, s));
+    RGA_HIP_CHECK(
+        hipMemcpyAsync(h_path_len_, arena_.path_len, na * 4, hipMemcpyDeviceToHost, s));
+  } else {
+    RGA_HIP_CHECK(hipMemcpyAsync(h_bp_, arena_.bp, bp_records_ * sizeof(AlnBpRecord),
+                                 hipMemcpyDeviceToHost, s));
+  }
   RGA_HIP_CHECK(hipMemcpyAsync(h_status_, arena_.status, na * 4, hipMemcpyDeviceToHost, s));
   RGA_HIP_CHECK(hipMemcpyAsync(h_edit_, arena_.edit_distance, na * 4, hipMemcpyDeviceToHost, s));
   RGA_HIP_CHECK(hipStreamSynchronize(s));
@@ -406,11 +458,50 @@ std::string AlignerBatch::cigar_of(uint32_t slot) const {
   return cigar;
 }
 
+std::vector<std::pair<uint32_t, uint32_t>> AlignerBatch::breaking_points_of(
+    uint32_t slot) const {
+  std::vector<std::pair<uint32_t, uint32_t>> points;
+  if (h_status_[slot] != kAlnOk) {
+    return points;
+  }
+  const AlnDesc& d = h_descs_[slot];
+  const AlnBpRecord* recs = h_bp_ + d.bp_offset;
+  points.reserve(2 * static_cast<size_t>(d.bp_count));
+  for (uint32_t w = 0; w < d.bp_count; ++w) {
+    if (recs[w].last_t == kAlnBpNone) {
+      continue;  // window without a match
+    }
+    points.emplace_back(recs[w].first_t, recs[w].first_q);
+    points.emplace_back(recs[w].last_t, recs[w].last_q);
+  }
+  return points;
+}
+
 uint32_t AlignerBatch::align_and_emit(uint32_t window_length) {
   if (overlaps_.empty()) {
     return 0;
   }
   run();
+  if (window_length_ > 0) {
+    // breaking-point mode: a few records per overlap, nothing worth threads.
+    // An overlap without a single matched window stays untouched, as it
+    // does on the CIGAR route (the CPU pass realigns it to the same end).
+    uint32_t failed_bp = 0;
+    for (size_t i = 0; i < overlaps_.size(); ++i) {
+      if (overlaps_[i] == nullptr) {
+        continue;
+      }
+      if (h_status_[i] != kAlnOk) {
+        ++failed_bp;
+        continue;
+      }
+      auto points = breaking_points_of(static_cast<uint32_t>(i));
+      if (!points.empty()) {
+        overlaps_[i]->set_breaking_points(std::move(points));
+      }
+    }
+    return failed_bp;
+  }
   // CIGAR strings are independent per slot: build them on a few threads
   // (the run-length walk over ~30 kbp paths x thousands of alignments is
   // otherwise a serial tail after every batch round)
@@ -464,6 +555,8 @@ void AlignerBatch::reset() {
   seq_bytes_ = 0;
   path_bytes_ = 0;
   tb_reserved_ = 0;
+  bp_records_ = 0;
+  window_length_ = 0;
 }
 
 }  // namespace rga::hip

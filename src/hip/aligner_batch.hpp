@@ -31,23 +31,39 @@ class AlignerBatch {
   // only — callable under the shared queue lock). Returns false when the
   // batch is full; never_fits is set when this overlap cannot run on the GPU
   // at all. The actual copies happen in pack().
+  // window_length > 0 reserves the overlap in breaking-point mode (below),
+  // with the overlap's own target / query origins.
   bool add_overlap(Overlap* overlap, const std::vector<std::unique_ptr<Sequence>>& sequences,
-                   bool* never_fits);
+                   bool* never_fits, uint32_t window_length = 0);
 
   // Raw-span variant (testing / direct use): returns the slot index, -1 when
   // the batch is full, -2 when the pair can never run here: empty or over-long
   // sequences, or non-ACGT bytes in both of them (checked unless
   // scan_non_acgt is false, for callers that already know one side is pure
   // A/C/G/T).
+  //
+  // window_length selects what the batch produces. 0: a path per alignment
+  // (cigar_of). > 0: breaking points per alignment (breaking_points_of) for
+  // window_length slices of the target, with t[0] at global target position
+  // t_origin and q[0] at query position q_origin; the kernel then writes one
+  // 16-byte record per slice instead of the path. A batch holds one
+  // window_length at a time: a reservation with another one gets -1 (flush
+  // first), and one whose records alone exceed the record arena gets -2.
   int32_t reserve_span(const char* q, uint32_t q_len, const char* t, uint32_t t_len,
-                       bool scan_non_acgt = true);
+                       bool scan_non_acgt = true, uint32_t window_length = 0,
+                       uint32_t t_origin = 0, uint32_t q_origin = 0);
 
-  // Runs the kernel over everything reserved (pack + sub-launches + D2H).
+  // Runs the kernel over everything reserved (pack + sub-launches + D2H). In
+  // breaking-point mode the records come back instead of path / path_len.
   void run();
   // Post-run accessors per slot.
   int32_t status_of(uint32_t slot) const { return h_status_[slot]; }
   int32_t edit_distance_of(uint32_t slot) const { return h_edit_[slot]; }
-  std::string cigar_of(uint32_t slot) const;
+  std::string cigar_of(uint32_t slot) const;  // path mode only
+  // Breaking-point mode only: (t, q) of the first match and one past the
+  // last match of every slice that has a match, in target order. Empty for a
+  // non-zero status.
+  std::vector<std::pair<uint32_t, uint32_t>> breaking_points_of(uint32_t slot) const;
 
   // Copies every reserved span into the pinned staging buffers. Called
   // outside the queue lock so fills from different batches proceed in
@@ -56,9 +72,11 @@ class AlignerBatch {
 
   uint32_t size() const { return static_cast<uint32_t>(overlaps_.size()); }
 
-  // Runs the kernel (possibly several sub-launches), writes CIGAR strings
-  // into the accepted overlaps AND walks them into breaking points right on
-  // the emit threads (window_length > 0) — the walk overlaps the other
+  // Runs the kernel (possibly several sub-launches) and hands the result to
+  // the accepted overlaps. Overlaps reserved in breaking-point mode get their
+  // breaking points straight from the kernel's records. Overlaps reserved in
+  // path mode get a CIGAR string, which window_length > 0 then walks into
+  // breaking points right on the emit threads — the walk overlaps the other
   // batches' kernels instead of serializing in the post-GPU CPU pass.
   // Returns how many overlaps fell back (band-edge -> CPU aligner).
   uint32_t align_and_emit(uint32_t window_length = 0);
@@ -77,6 +95,7 @@ class AlignerBatch {
   uint32_t band_k_;  // blocks per band (4, 8 or 16)
 
   size_t seq_cap_, path_cap_;
+  size_t bp_cap_;  // window records
   uint64_t tb_cap_u64_, s_cap_i32_, peq_cap_u64_;
   uint32_t max_alignments_;
 
@@ -88,6 +107,7 @@ class AlignerBatch {
   int32_t* h_edit_ = nullptr;
   uint32_t* h_order_ = nullptr;
   AlnWaveDesc* h_waves_ = nullptr;
+  AlnBpRecord* h_bp_ = nullptr;
 
   void* d_pool_ = nullptr;
   AlnDeviceArena arena_{};
@@ -97,6 +117,8 @@ class AlignerBatch {
   size_t seq_bytes_ = 0;
   size_t path_bytes_ = 0;
   uint64_t tb_reserved_ = 0;  // u64 units of per-column state reserved
+  size_t bp_records_ = 0;     // window records reserved
+  uint32_t window_length_ = 0;  // of the current fill; 0 = path mode
   std::vector<Overlap*> overlaps_;
   struct PendingSpan {
     const char* q;

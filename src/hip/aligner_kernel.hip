@@ -51,7 +51,11 @@ __device__ inline int32_t score_at(int32_t S, uint64_t Pv, uint64_t Mv, uint32_t
   return S - (__popcll(Pv & mask) - __popcll(Mv & mask));
 }
 
-template <int K>
+// kEmitPath selects what the traceback produces. Both modes take the same
+// moves in the same order; path mode stores one op byte per move, while
+// breaking-point mode keeps the current window's record in registers and
+// stores it (one 16-byte write) when the walk leaves the window.
+template <int K, bool kEmitPath>
 __launch_bounds__(kLanes)
 __global__ void myers_kernel(AlnDeviceArena a, uint32_t num_align) {
   const uint32_t wave = blockIdx.x;
@@ -214,6 +218,27 @@ __global__ void myers_kernel(AlnDeviceArena a, uint32_t num_align) {
   // ---- traceback: O(1) per step via stored column states ----
   uint8_t* path = a.path + desc.path_offset;
   uint32_t plen = 0;
+  // Breaking-point mode walks the target's windows from the last one down.
+  // `w` is the current window's record index and `lo` its lowest target
+  // position; consuming a target position below `lo` closes the window. The
+  // one modulo per lane here stands in for a division on every step.
+  AlnBpRecord* recs = nullptr;
+  AlnBpRecord rec = {kAlnBpNone, kAlnBpNone, kAlnBpNone, kAlnBpNone};
+  int32_t w = 0;
+  uint32_t lo = 0;
+  if constexpr (!kEmitPath) {
+    recs = a.bp + desc.bp_offset;
+    w = static_cast<int32_t>(desc.bp_count) - 1;
+    const uint32_t t_last = desc.t_origin + static_cast<uint32_t>(m) - 1;
+    lo = t_last - t_last % a.window_length;
+  }
+  auto close_window = [&]() {
+    if (w >= 0) {  // bp_count covers every window of the span; never stores below it
+      recs[w] = rec;
+    }
+    --w;
+    rec = {kAlnBpNone, kAlnBpNone, kAlnBpNone, kAlnBpNone};
+  };
   int32_t i = n, j = m;
   while (st == kAlnOk && i > 0 && j > 0) {
     const int32_t babs = (i - 1) >> 6;
@@ -242,17 +267,44 @@ __global__ void myers_kernel(AlnDeviceArena a, uint32_t num_align) {
                          base_code(q[i - 1]) >= 4)
                             ? 1
                             : 0;
+    // global position of the target base a diagonal or left move consumes
+    const uint32_t tg = desc.t_origin + static_cast<uint32_t>(j) - 1;
     if (D_diag + sub == D) {
-      path[plen++] = 0;  // M
+      if constexpr (kEmitPath) {
+        path[plen++] = 0;  // M
+      } else {
+        if (tg < lo) {
+          close_window();
+          lo -= a.window_length;
+        }
+        // walking backwards: the first match met is the window's last one,
+        // every later match is its first so far
+        const uint32_t qg = desc.q_origin + static_cast<uint32_t>(i) - 1;
+        if (rec.last_t == kAlnBpNone) {
+          rec.last_t = tg + 1;
+          rec.last_q = qg + 1;
+        }
+        rec.first_t = tg;
+        rec.first_q = qg;
+      }
       --i;
       --j;
       D = D_diag;
     } else if (D_left + 1 == D) {
-      path[plen++] = 2;  // D (consume target)
+      if constexpr (kEmitPath) {
+        path[plen++] = 2;  // D (consume target)
+      } else {
+        if (tg < lo) {
+          close_window();
+          lo -= a.window_length;
+        }
+      }
       --j;
       D = D_left;
     } else if ((D - vd) + 1 == D) {
-      path[plen++] = 1;  // I (consume query)
+      if constexpr (kEmitPath) {
+        path[plen++] = 1;  // I (consume query)
+      }
       --i;
       D = D - vd;
     } else {
@@ -260,35 +312,60 @@ __global__ void myers_kernel(AlnDeviceArena a, uint32_t num_align) {
       break;
     }
   }
-  if (st == kAlnOk) {
-    while (i > 0) {
-      path[plen++] = 1;
-      --i;
+  if constexpr (kEmitPath) {
+    if (st == kAlnOk) {
+      while (i > 0) {
+        path[plen++] = 1;
+        --i;
+      }
+      while (j > 0) {
+        path[plen++] = 2;
+        --j;
+      }
     }
-    while (j > 0) {
-      path[plen++] = 2;
-      --j;
+    a.path_len[idx] = (st == kAlnOk) ? plen : 0;
+  } else {
+    // The tail is a run of insertions (i > 0: no target consumed, nothing to
+    // do) or of deletions (j > 0: every target position left is unmatched).
+    // Either way the current window closes as it stands and every window
+    // below it has no match, however many the deletion run crosses.
+    if (st == kAlnOk) {
+      while (w >= 0) {
+        close_window();
+      }
     }
   }
-  a.path_len[idx] = (st == kAlnOk) ? plen : 0;
   a.status[idx] = st;
 }
 
 }  // namespace
 
+namespace {
+template <int K>
+void launch_k(const AlnDeviceArena& arena, uint32_t num_waves, uint32_t num_align,
+              bool emit_path, hipStream_t s) {
+  if (emit_path) {
+    hipLaunchKernelGGL((myers_kernel<K, true>), dim3(num_waves), dim3(kLanes), 0, s, arena,
+                       num_align);
+  } else {
+    hipLaunchKernelGGL((myers_kernel<K, false>), dim3(num_waves), dim3(kLanes), 0, s, arena,
+                       num_align);
+  }
+}
+}  // namespace
+
 void launch_aligner_kernel(const AlnDeviceArena& arena, uint32_t num_waves, uint32_t num_align,
-                           uint32_t band_k, void* stream) {
+                           uint32_t band_k, bool emit_path, void* stream) {
   auto s = static_cast<hipStream_t>(stream);
   switch (band_k) {
     case 4:
-      hipLaunchKernelGGL(myers_kernel<4>, dim3(num_waves), dim3(kLanes), 0, s, arena, num_align);
+      launch_k<4>(arena, num_waves, num_align, emit_path, s);
       break;
     case 8:
-      hipLaunchKernelGGL(myers_kernel<8>, dim3(num_waves), dim3(kLanes), 0, s, arena, num_align);
+      launch_k<8>(arena, num_waves, num_align, emit_path, s);
       break;
     default:
-      hipLaunchKernelGGL(myers_kernel<16>, dim3(num_waves), dim3(kLanes), 0, s, arena,
-                         num_align);
+      launch_k<16>(arena, num_waves, num_align, emit_path, s);
       break;
   }
 }

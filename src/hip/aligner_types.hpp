@@ -34,7 +34,22 @@ struct AlnDesc {
   uint32_t t_offset;
   uint32_t t_len;      // m (DP columns)
   uint32_t path_offset;  // bytes into the path arena (capacity q_len+t_len)
+  // breaking-point mode only (see AlnBpRecord)
+  uint32_t t_origin;   // global target position of t[0]
+  uint32_t q_origin;   // global query position of q[0]
+  uint32_t bp_offset;  // records into the record arena
+  uint32_t bp_count;   // window slices the target span touches
 };
+
+// Breaking-point mode: one record per window_length slice of the target
+// (slices aligned to target coordinate 0) that the span [t_origin,
+// t_origin + t_len) touches, in ascending target order. A slice without a
+// match holds kAlnBpNone in every field.
+struct alignas(16) AlnBpRecord {
+  uint32_t first_t, first_q;  // first matched (target, query) position
+  uint32_t last_t, last_q;    // last matched position + 1 on both axes
+};
+constexpr uint32_t kAlnBpNone = 0xffffffffu;
 
 // Per-wave offsets into the shared arenas (element units). Lanes of a wave
 // share one region so per-column stores coalesce across the 64 alignments.
@@ -58,6 +73,8 @@ struct AlnDeviceArena {
   uint32_t* path_len;        // per alignment (original index)
   int32_t* status;           // per alignment
   int32_t* edit_distance;    // per alignment (diagnostic)
+  AlnBpRecord* bp;           // breaking-point mode: window records
+  uint32_t window_length;    // breaking-point mode: slice width (> 0)
   uint32_t lanes_per_wave;   // alignments packed per 64-lane wave; fewer
                              // than 64 when the job is too small to give
                              // every CU multiple waves (latency hiding)
@@ -65,8 +82,11 @@ struct AlnDeviceArena {
 };
 
 // Launches the K-block Myers kernel over `num_align` sorted alignments
-// packed arena.lanes_per_wave to a wave. band_k must be 4, 8 or 16.
+// packed arena.lanes_per_wave to a wave. band_k must be 4, 8 or 16. With
+// emit_path the traceback writes path / path_len; without it the traceback
+// writes the window records (arena.bp, arena.window_length) and leaves the
+// path arena alone.
 void launch_aligner_kernel(const AlnDeviceArena& arena, uint32_t num_waves, uint32_t num_align,
-                           uint32_t band_k, void* stream);
+                           uint32_t band_k, bool emit_path, void* stream);
 
 }  // namespace rga::hip

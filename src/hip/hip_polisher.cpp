@@ -10,6 +10,7 @@
 #include <chrono>
 #include <memory>
 #include <mutex>
+#include <stdexcept>
 #include <string>
 #include <thread>
 #include <tuple>
@@ -211,7 +212,8 @@ class HipPolisher : public Polisher {
               continue;
             }
             bool never_fits = false;
-            if (batch->add_overlap(o, sequences_, &never_fits)) {
+            // window_length > 0: the kernel emits the breaking points itself
+            if (batch->add_overlap(o, sequences_, &never_fits, config_.window_length)) {
               ++pulled;
               ++next_overlap;
             } else if (never_fits) {
@@ -536,6 +538,63 @@ std::vector<std::tuple<std::string, int32_t, int32_t>> align_pairs(
                                     static_cast<uint32_t>(pairs[i].first.size()),
                                     pairs[i].second.data(),
                                     static_cast<uint32_t>(pairs[i].second.size()));
+    }
+  }
+  flush(pairs.size());
+  return out;
+}
+
+// Direct GPU breaking points of raw (query, target) pairs — the kernel's
+// breaking-point traceback mode, for testing against
+// breaking_points_from_cigar over align_pairs' CIGAR. Pair k's target starts
+// at global position t_begins[k] and its query at q_begins[k] (0 when the
+// list is empty). Returns (points, edit_distance, status) per pair; points
+// are empty for a non-zero status.
+std::vector<std::tuple<std::vector<std::pair<uint32_t, uint32_t>>, int32_t, int32_t>>
+breaking_points_pairs(const std::vector<std::pair<std::string, std::string>>& pairs,
+                      uint32_t window_length, const std::vector<uint32_t>& t_begins,
+                      const std::vector<uint32_t>& q_begins, uint32_t band_width) {
+  if (window_length == 0) {
+    throw std::invalid_argument("breaking_points_pairs: window_length must be positive");
+  }
+  if ((!t_begins.empty() && t_begins.size() != pairs.size()) ||
+      (!q_begins.empty() && q_begins.size() != pairs.size())) {
+    throw std::invalid_argument("breaking_points_pairs: one begin per pair, or none");
+  }
+  std::vector<std::tuple<std::vector<std::pair<uint32_t, uint32_t>>, int32_t, int32_t>> out(
+      pairs.size());
+  if (pairs.empty()) {
+    return out;
+  }
+  AlignerBatch batch(0, 4ull << 30, band_width);
+  size_t begin = 0;
+  std::vector<int32_t> slots(pairs.size(), -1);
+  auto flush = [&](size_t end) {
+    batch.run();
+    for (size_t i = begin; i < end; ++i) {
+      if (slots[i] >= 0) {
+        out[i] = {batch.breaking_points_of(slots[i]), batch.edit_distance_of(slots[i]),
+                  batch.status_of(slots[i])};
+      } else {
+        out[i] = {std::vector<std::pair<uint32_t, uint32_t>>(), -1, kAlnNotRun};
+      }
+    }
+    batch.reset();
+    begin = end;
+  };
+  auto reserve = [&](size_t i) {
+    return batch.reserve_span(pairs[i].first.data(),
+                              static_cast<uint32_t>(pairs[i].first.size()),
+                              pairs[i].second.data(),
+                              static_cast<uint32_t>(pairs[i].second.size()), true,
+                              window_length, t_begins.empty() ? 0 : t_begins[i],
+                              q_begins.empty() ? 0 : q_begins[i]);
+  };
+  for (size_t i = 0; i < pairs.size(); ++i) {
+    slots[i] = reserve(i);
+    if (slots[i] == -1) {
+      flush(i);
+      slots[i] = reserve(i);
     }
   }
   flush(pairs.size());

@@ -10,6 +10,8 @@
 #include <pybind11/stl.h>
 
 #include <memory>
+#include <optional>
+#include <stdexcept>
 #include <string>
 #include <utility>
 #include <vector>
@@ -25,6 +27,10 @@ int runtime_device_count();  // provided by the HIP backend (or the stub)
 void runtime_device_synchronize();
 std::vector<std::tuple<std::string, int32_t, int32_t>> align_pairs(
     const std::vector<std::pair<std::string, std::string>>& pairs, uint32_t band_width);
+std::vector<std::tuple<std::vector<std::pair<uint32_t, uint32_t>>, int32_t, int32_t>>
+breaking_points_pairs(const std::vector<std::pair<std::string, std::string>>& pairs,
+                      uint32_t window_length, const std::vector<uint32_t>& t_begins,
+                      const std::vector<uint32_t>& q_begins, uint32_t band_width);
 std::vector<std::pair<std::string, bool>> poa_windows_gpu(
     const std::vector<std::vector<std::tuple<std::string, std::string, uint32_t, uint32_t>>>&
         window_layers,
@@ -82,6 +88,33 @@ std::string align_cigar_py(const std::string& q, const std::string& t) {
   py::gil_scoped_release release;
   return rga::align_global_cigar(q.c_str(), static_cast<uint32_t>(q.size()), t.c_str(),
                                  static_cast<uint32_t>(t.size()));
+}
+
+// The CIGAR walk the pipeline uses (rga::breaking_points_from_cigar): the
+// oracle for the GPU aligner's breaking-point mode. The span must be the one
+// the CIGAR covers; the walk itself trusts its caller on that.
+std::vector<std::pair<uint32_t, uint32_t>> breaking_points_from_cigar_py(
+    const std::string& cigar, uint32_t window_length, uint32_t t_begin, uint32_t t_end,
+    uint32_t q_begin) {
+  if (window_length == 0) {
+    throw std::invalid_argument("breaking_points_from_cigar: window_length must be positive");
+  }
+  uint64_t t_used = 0;
+  for (size_t i = 0, j = 0; i < cigar.size(); ++i) {
+    const char op = cigar[i];
+    if (op >= '0' && op <= '9') {
+      continue;
+    }
+    if (op == 'M' || op == '=' || op == 'X' || op == 'D' || op == 'N') {
+      t_used += static_cast<uint64_t>(atoll(cigar.c_str() + j));
+    }
+    j = i + 1;
+  }
+  if (t_end <= t_begin || t_used != t_end - t_begin) {
+    throw std::invalid_argument(
+        "breaking_points_from_cigar: the CIGAR does not cover [t_begin, t_end)");
+  }
+  return rga::breaking_points_from_cigar(cigar, window_length, t_begin, t_end, q_begin);
 }
 
 std::string reverse_complement(const std::string& s) {
@@ -242,6 +275,24 @@ PYBIND11_MODULE(_racon, m) {
         },
         py::arg("pairs"), py::arg("band_width") = 0,
         "GPU Myers aligner on raw (query, target) pairs -> (cigar, edit_distance, status)");
+  m.def("gpu_breaking_points",
+        [](const std::vector<std::pair<std::string, std::string>>& pairs, uint32_t window_length,
+           const std::optional<std::vector<uint32_t>>& t_begins,
+           const std::optional<std::vector<uint32_t>>& q_begins, uint32_t band_width) {
+          py::gil_scoped_release release;
+          return rga::hip::breaking_points_pairs(
+              pairs, window_length, t_begins.value_or(std::vector<uint32_t>()),
+              q_begins.value_or(std::vector<uint32_t>()), band_width);
+        },
+        py::arg("pairs"), py::arg("window_length"), py::arg("t_begins") = py::none(),
+        py::arg("q_begins") = py::none(), py::arg("band_width") = 0,
+        "GPU Myers aligner in breaking-point mode on raw (query, target) pairs whose "
+        "target / query start at t_begins[k] / q_begins[k] -> ([(t, q), ...], "
+        "edit_distance, status)");
+  m.def("breaking_points_from_cigar", &breaking_points_from_cigar_py, py::arg("cigar"),
+        py::arg("window_length"), py::arg("t_begin"), py::arg("t_end"), py::arg("q_begin"),
+        "Per-window (target, query) breaking points of a CIGAR over [t_begin, t_end): "
+        "first match and last match + 1 of every window that has a match.");
   m.def("reverse_complement", &reverse_complement, py::arg("sequence"));
   // window-level CPU-vs-GPU differ: identical raw-window inputs through
   // both engines (layers = [(seq, qual, begin, end)], slot 0 = backbone)
