@@ -17,9 +17,11 @@
 // per-row scalar pointer-chase (sorted -> letter/in-count/first-edge ->
 // pred rank) is replaced by one packed u64 `row_desc` per rank built
 // LANE-PARALLEL after each topological sort, and the DP records a move byte
-// per cell so the serial traceback is one byte load per step. The serial
-// graph phases stay in global memory and are hidden by the deep window
-// co-residency, as in v1.
+// per cell so the serial traceback is one byte load per step. The graph
+// phases stay in global memory and are hidden by the deep window
+// co-residency, as in v1. Of them only the traceback and the Kahn FIFO,
+// whose order is the result, still run on lane 0: threading the path into
+// the graph (add_alignment_d) handles 64 sequence positions per step.
 //
 // Semantics mirror the CPU engine (src/align/poa.cpp) so GPU results are
 // deterministic and window-content-only (reference racon-gpu pins separate
@@ -167,167 +169,178 @@ struct WindowCtx : PoaSlabs {
   int32_t status;
 };
 
-// ---------- serial (lane 0) graph helpers ----------
+// ---------- graph helpers ----------
 
 __device__ inline uint16_t out_edge_of(const WindowCtx& c, uint32_t node, uint32_t e) {
   return c.out_edges[node * kMaxE + e];
 }
 
-__device__ inline bool add_edge_d(WindowCtx& c, uint32_t a, uint32_t b, int32_t w) {
-  uint32_t n_out = c.out_cnt[a];
+// Adds weight w to edge a -> b, appending the edge when it is new. One lane
+// per edge; returns kPoaOk or kPoaEdgeOverflow.
+__device__ inline int32_t add_edge_d(const WindowCtx& c, uint32_t a, uint32_t b, int32_t w) {
+  const uint32_t n_out = c.out_cnt[a];
   for (uint32_t e = 0; e < n_out; ++e) {
     if (out_edge_of(c, a, e) == b) {
-      uint32_t n_in = c.in_cnt[b];
+      const uint32_t n_in = c.in_cnt[b];
       for (uint32_t f = 0; f < n_in; ++f) {
         if (c.in_edges[b * kMaxE + f] == a) {
           c.in_weights[b * kMaxE + f] += w;
-          return true;
-        }
-      }
-      return true;  // unreachable for a consistent graph
-    }
-  }
-  if (n_out >= kMaxE || c.in_cnt[b] >= kMaxE) {
-    c.status = kPoaEdgeOverflow;
-    return false;
-  }
-  c.out_edges[a * kMaxE + n_out] = static_cast<uint16_t>(b);
-  c.out_cnt[a] = static_cast<uint8_t>(n_out + 1);
-  uint32_t n_in = c.in_cnt[b];
-  c.in_edges[b * kMaxE + n_in] = static_cast<uint16_t>(a);
-  c.in_weights[b * kMaxE + n_in] = w;
-  c.in_cnt[b] = static_cast<uint8_t>(n_in + 1);
-  return true;
-}
-
-__device__ inline int32_t add_node_d(WindowCtx& c, uint8_t letter) {
-  if (c.num_nodes >= c.MN) {
-    c.status = kPoaNodeOverflow;
-    return -1;
-  }
-  uint32_t id = c.num_nodes++;
-  c.letters[id] = letter;
-  c.in_cnt[id] = 0;
-  c.out_cnt[id] = 0;
-  c.ring_cnt[id] = 0;
-  c.nseq[id] = 0;
-  return static_cast<int32_t>(id);
-}
-
-// Threads the traceback path (stored reversed in aln_*) into the graph.
-// Mirrors Graph::add_alignment (src/align/poa.cpp).
-__device__ void add_alignment_d(WindowCtx& c, const uint8_t* seq,
-                                const uint8_t* wts, uint32_t len, int32_t aln_len) {
-  // first/last aligned sequence positions
-  int32_t first_pos = -1, last_pos = -1;
-  for (int32_t k = aln_len - 1; k >= 0; --k) {  // reversed storage -> forward walk
-    if (c.aln_seq[k] != -1) {
-      if (first_pos == -1) {
-        first_pos = c.aln_seq[k];
-      }
-      last_pos = c.aln_seq[k];
-    }
-  }
-
-  int32_t head = -1;
-  int32_t prev_weight = 0;
-  int32_t last_counted = -1;
-
-  auto link = [&](int32_t a, int32_t b, int32_t w) {
-    if (!add_edge_d(c, a, b, w)) {
-      return;
-    }
-    if (a != last_counted) {
-      ++c.nseq[a];
-    }
-    ++c.nseq[b];
-    last_counted = b;
-  };
-
-  if (first_pos == -1) {
-    // fully unaligned layer: append as a fresh chain
-    first_pos = len;  // head chain covers the whole sequence below
-  }
-
-  // head chain: seq[0 .. first_pos)
-  for (int32_t p = 0; p < first_pos; ++p) {
-    int32_t id = add_node_d(c, seq[p]);
-    if (id < 0) return;
-    if (head != -1) {
-      link(head, id, prev_weight + wts[p]);
-    }
-    head = id;
-    prev_weight = wts[p];
-  }
-
-  // aligned middle
-  for (int32_t k = aln_len - 1; k >= 0; --k) {
-    int32_t spos = c.aln_seq[k];
-    if (spos == -1) {
-      continue;
-    }
-    uint8_t letter = seq[spos];
-    int32_t node = c.aln_nodes[k];
-    int32_t new_id;
-    if (node == -1) {
-      new_id = add_node_d(c, letter);
-      if (new_id < 0) return;
-    } else if (c.letters[node] == letter) {
-      new_id = node;
-    } else {
-      new_id = -1;
-      uint32_t nr = c.ring_cnt[node];
-      for (uint32_t r = 0; r < nr; ++r) {
-        uint16_t aid = c.ring[node * kMaxR + r];
-        if (c.letters[aid] == letter) {
-          new_id = aid;
           break;
         }
       }
-      if (new_id == -1) {
-        new_id = add_node_d(c, letter);
-        if (new_id < 0) return;
-        // join the ring: new node linked with node and all its partners
-        if (nr >= kMaxR) {
-          c.status = kPoaRingOverflow;
-          return;
-        }
-        for (uint32_t r = 0; r < nr; ++r) {
-          uint16_t aid = c.ring[node * kMaxR + r];
-          c.ring[new_id * kMaxR + r] = aid;
-          uint32_t arc = c.ring_cnt[aid];
-          if (arc >= kMaxR) {
-            c.status = kPoaRingOverflow;
-            return;
+      return kPoaOk;  // a miss is unreachable for a consistent graph
+    }
+  }
+  const uint32_t n_in = c.in_cnt[b];
+  if (n_out >= kMaxE || n_in >= kMaxE) {
+    return kPoaEdgeOverflow;
+  }
+  c.out_edges[a * kMaxE + n_out] = static_cast<uint16_t>(b);
+  c.out_cnt[a] = static_cast<uint8_t>(n_out + 1);
+  c.in_edges[b * kMaxE + n_in] = static_cast<uint16_t>(a);
+  c.in_weights[b * kMaxE + n_in] = w;
+  c.in_cnt[b] = static_cast<uint8_t>(n_in + 1);
+  return kPoaOk;
+}
+
+// First non-zero status of any lane (wave-uniform), kPoaOk when all are.
+__device__ inline int32_t wave_first_status(int32_t status) {
+  const uint64_t bad = __ballot(status != kPoaOk);
+  return bad == 0 ? kPoaOk : __shfl(status, __ffsll(static_cast<long long>(bad)) - 1, kLanes);
+}
+
+// Threads the traceback path into the graph, 64 sequence positions at a
+// time. Call from ALL lanes. Mirrors Graph::add_alignment (src/align/poa.cpp)
+// and builds element for element the graph its serial walk builds.
+//
+// Input: aln_nodes[p] = graph node sequence position p is aligned to, or -1
+// for an insertion (traceback_d). The traceback always runs from column len
+// to (0,0), so every position 0..len-1 has its entry: a layer with no
+// aligned position at all (the head/tail chains of the CPU code) cannot
+// reach this function, its positions are all insertions against row 0.
+//
+// Sweep A resolves position p to a node id — the aligned node when the
+// letter matches, a ring partner with that letter, else a new node — and
+// leaves it in aln_seq[p]. New ids are num_nodes + the number of earlier new
+// positions (ballot/popcount inside a block, running base across blocks),
+// which is the order the serial walk hands them out in. Sweep B gives lane p
+// the edge id[p-1] -> id[p] and the coverage count of id[p].
+//
+// No atomics, because no two lanes write the same element. The alignment
+// path is a path in the DAG, so its nodes are mutually reachable, while the
+// members of one aligned ring are mutually unreachable: a new member is hung
+// between the path predecessor and successor of the node it aligns to, and
+// later edges only connect pairs that were already reachable. Hence the
+// positions of one layer touch pairwise different rings (ring, ring_cnt:
+// one writer per ring), the resolved ids are pairwise different, and every
+// id is the source of exactly one edge and the target of exactly one
+// (out_edges/out_cnt of id[p-1] and in_edges/in_cnt/in_weights/nseq of id[p]
+// belong to lane p alone).
+//
+// Any overflow is terminal for the window (the layer loop stops and the
+// window goes to the CPU), so the graph left behind by a failing call is
+// unspecified; only "fails whenever the serial walk would" is kept.
+__device__ void add_alignment_d(WindowCtx& c, const uint8_t* seq, const uint8_t* wts,
+                                uint32_t len, int lane) {
+  int32_t status = kPoaOk;
+  uint32_t next_id = c.num_nodes;
+
+  // ---- sweep A: position -> node id ----
+  for (uint32_t blk = 0; blk < len; blk += kLanes) {
+    const uint32_t p = blk + lane;
+    const bool active = p < len;
+    uint8_t letter = 0;
+    int32_t node = -1;
+    int32_t id = -1;
+    uint32_t nr = 0;
+    if (active) {
+      letter = seq[p];
+      node = c.aln_nodes[p];
+      if (node != -1) {
+        if (c.letters[node] == letter) {
+          id = node;
+        } else {
+          nr = c.ring_cnt[node];
+          for (uint32_t r = 0; r < nr; ++r) {
+            const uint16_t aid = c.ring[node * kMaxR + r];
+            if (c.letters[aid] == letter) {
+              id = aid;
+              break;
+            }
           }
-          c.ring[aid * kMaxR + arc] = static_cast<uint16_t>(new_id);
-          c.ring_cnt[aid] = static_cast<uint8_t>(arc + 1);
         }
-        c.ring[new_id * kMaxR + nr] = static_cast<uint16_t>(node);
-        c.ring_cnt[new_id] = static_cast<uint8_t>(nr + 1);
-        uint32_t nrc = c.ring_cnt[node];
-        c.ring[node * kMaxR + nrc] = static_cast<uint16_t>(new_id);
-        c.ring_cnt[node] = static_cast<uint8_t>(nrc + 1);
       }
     }
-    if (head != -1) {
-      link(head, new_id, prev_weight + wts[spos]);
+    const bool is_new = active && id == -1;
+    const uint64_t new_mask = __ballot(is_new);
+    if (is_new) {
+      const uint32_t nid = next_id + __popcll(new_mask & ((1ull << lane) - 1));
+      id = static_cast<int32_t>(nid);
+      if (nid >= c.MN) {
+        status = kPoaNodeOverflow;
+      } else {
+        c.letters[nid] = letter;
+        c.in_cnt[nid] = 0;
+        c.out_cnt[nid] = 0;
+        c.ring_cnt[nid] = 0;
+        c.nseq[nid] = 0;
+        if (node != -1) {
+          // join the ring: new node linked with node and all its partners
+          if (nr >= kMaxR) {
+            status = kPoaRingOverflow;
+          } else {
+            for (uint32_t r = 0; r < nr; ++r) {
+              const uint16_t aid = c.ring[node * kMaxR + r];
+              c.ring[nid * kMaxR + r] = aid;
+              const uint32_t arc = c.ring_cnt[aid];
+              if (arc >= kMaxR) {
+                status = kPoaRingOverflow;
+                break;
+              }
+              c.ring[aid * kMaxR + arc] = static_cast<uint16_t>(nid);
+              c.ring_cnt[aid] = static_cast<uint8_t>(arc + 1);
+            }
+            c.ring[nid * kMaxR + nr] = static_cast<uint16_t>(node);
+            c.ring_cnt[nid] = static_cast<uint8_t>(nr + 1);
+            c.ring[node * kMaxR + nr] = static_cast<uint16_t>(nid);
+            c.ring_cnt[node] = static_cast<uint8_t>(nr + 1);
+          }
+        }
+      }
     }
-    head = new_id;
-    prev_weight = wts[spos];
-  }
-
-  // tail chain: seq[last_pos+1 .. len)
-  for (int32_t p = (last_pos == -1 ? len : last_pos + 1); p < static_cast<int32_t>(len); ++p) {
-    int32_t id = add_node_d(c, seq[p]);
-    if (id < 0) return;
-    if (head != -1) {
-      link(head, id, prev_weight + wts[p]);
+    next_id += __popcll(new_mask);
+    if (active) {
+      c.aln_seq[p] = id;
     }
-    head = id;
-    prev_weight = wts[p];
   }
+  status = wave_first_status(status);
+  if (status != kPoaOk) {
+    c.status = status;
+    return;
+  }
+  c.num_nodes = next_id;
+  __syncthreads();  // ids and new nodes -> visible to the lanes of sweep B
 
+  // ---- sweep B: edges id[p-1] -> id[p], coverage ----
+  // (a one-base layer has no edge and, as in the serial walk, counts nowhere)
+  if (len >= 2) {
+    for (uint32_t blk = 0; blk < len; blk += kLanes) {
+      const uint32_t p = blk + lane;
+      if (p < len) {
+        const uint32_t b = static_cast<uint32_t>(c.aln_seq[p]);
+        ++c.nseq[b];
+        if (p != 0 && status == kPoaOk) {
+          const uint32_t a = static_cast<uint32_t>(c.aln_seq[p - 1]);
+          status = add_edge_d(c, a, b, static_cast<int32_t>(wts[p - 1]) + wts[p]);
+        }
+      }
+    }
+    status = wave_first_status(status);
+    if (status != kPoaOk) {
+      c.status = status;
+      return;
+    }
+  }
   ++c.seqs_in_graph;
 }
 
@@ -1024,10 +1037,13 @@ __device__ __forceinline__ void dp_row(const WindowCtx c, SH& s, const LayerDp& 
 
 // ---------- serial (lane 0) traceback ----------
 
-// Walks the move bytes back from (best_row, len) to the origin; writes the
-// path (reversed) into aln_nodes / aln_seq and returns its length.
-__device__ int32_t traceback_d(WindowCtx& c, uint32_t best_row, uint32_t len) {
-  int32_t aln_len = 0;
+// Walks the move bytes back from (best_row, len) to the origin. The walk
+// ends at column 0, so it passes every sequence position exactly once:
+// aln_nodes[p] gets the node position p is aligned to, or -1 for an
+// insertion — indexed by position, which is what add_alignment_d loads 64
+// at a time. Path entries that consume a graph node only (up moves) thread
+// nothing into the graph and are not recorded.
+__device__ void traceback_d(WindowCtx& c, uint32_t best_row, uint32_t len) {
   uint32_t i = best_row, j = len;
   while (!(i == 0 && j == 0)) {
     uint32_t prev_i = i, prev_j = j;
@@ -1067,13 +1083,12 @@ __device__ int32_t traceback_d(WindowCtx& c, uint32_t best_row, uint32_t len) {
         }
       }
     }
-    c.aln_nodes[aln_len] = rec_node;
-    c.aln_seq[aln_len] = rec_seq;
-    ++aln_len;
+    if (rec_seq != -1) {
+      c.aln_nodes[rec_seq] = rec_node;
+    }
     i = prev_i;
     j = prev_j;
   }
-  return aln_len;
 }
 
 // ---------- the mega-kernel ----------
@@ -1185,19 +1200,22 @@ __global__ void poa_window_kernel(PoaDeviceArena a, uint32_t window_base,
     t_dp += lap();
     ++layers_done;
 
-    // ---- serial phases on lane 0 ----
+    // ---- serial traceback on lane 0 (its order is the result) ----
     if (lane == 0) {
-      const int32_t aln_len = traceback_d(c, best_row, len);
-      t_tb += lap();
-      if (c.status == kPoaOk) {
-        add_alignment_d(c, seq, wts, len, aln_len);
-      }
-      t_add += lap();
+      traceback_d(c, best_row, len);
     }
+    __syncthreads();  // lane 0's path -> visible to the whole wave
+    c.status = __shfl(c.status, 0, kLanes);
+    t_tb += lap();
 
-    // lane 0's graph updates must be visible to the whole wave
+    // ---- thread the path into the graph, all lanes ----
+    if (c.status == kPoaOk) {
+      add_alignment_d(c, seq, wts, len, lane);
+    }
+    // the graph updates must be visible to the whole wave
     __syncthreads();
-    // broadcast updated scalars from lane 0 to the wave
+    t_add += lap();
+    // add_alignment_d keeps these wave-uniform; lane 0 is the reference
     c.num_nodes = __shfl(c.num_nodes, 0, kLanes);
     c.seqs_in_graph = __shfl(c.seqs_in_graph, 0, kLanes);
     c.status = __shfl(c.status, 0, kLanes);

@@ -4,7 +4,8 @@
 // src/cuda/cudabatch.cpp (BatchConfig(1023, 200, 256, ...), add_poa_group /
 // generate_poa / get_consensus contract) — re-designed for CDNA4: one 64-lane
 // wavefront per window, full-width DP rows streamed through HBM as int16,
-// serial graph phases on lane 0 hidden by 16-32 co-resident windows per CU.
+// graph phases in global memory (traceback and Kahn FIFO on lane 0, path
+// threading on all lanes) hidden by 16-32 co-resident windows per CU.
 #pragma once
 
 #include <cstddef>
@@ -128,7 +129,9 @@ struct PoaWindowDesc {
 //   rank      node -> rank (Kahn scratch/queue and the topological order
 //             itself live in LDS)
 //   hb_*      heaviest-bundle running scores / predecessors
-//   aln_*     alignment node ids / sequence positions (traceback output)
+//   aln_nodes per sequence position: aligned node or -1 (traceback output)
+//   aln_seq   per sequence position: the node id it was threaded to
+//             (add_alignment_d); both use the first max layer length entries
 //   matrix    DP scores
 //   moves     DP move bytes: bits 0-1 {0=diag,1=up,2=left,3=invalid},
 //             bits 2-7 in-edge index of the chosen predecessor
