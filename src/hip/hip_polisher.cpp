@@ -427,22 +427,18 @@ int runtime_device_count() { return device_count(); }
 
 void runtime_device_synchronize() { RGA_HIP_CHECK(hipDeviceSynchronize()); }
 
-// Window-level CPU-vs-GPU differ entry: runs the HIP POA kernel directly on
-// raw windows (backbone first; layer spans in backbone coordinates), so a
-// divergent window found end-to-end can be isolated and replayed. Returns
-// (consensus, polished) per window — exactly what the pipeline would store.
-// Windows the GPU cannot run (< 3 layers, overflow) return the same CPU
-// fallback semantics as HipPolisher::polish.
-std::vector<std::pair<std::string, bool>> poa_windows_gpu(
-    const std::vector<std::vector<std::tuple<std::string, std::string, uint32_t, uint32_t>>>&
-        window_layers,
-    int8_t match, int8_t mismatch, int8_t gap, bool banded, bool trim, bool tgs) {
-  std::vector<std::pair<std::string, bool>> out(window_layers.size());
+using RawWindows =
+    std::vector<std::vector<std::tuple<std::string, std::string, uint32_t, uint32_t>>>;
+
+// Windows of the raw-layer entries below: slot 0 is the backbone, the rest
+// are (sequence, quality or "", begin, end) layers.
+static std::vector<std::shared_ptr<Window>> windows_from_layers(const RawWindows& window_layers,
+                                                                bool tgs, const char* caller) {
   std::vector<std::shared_ptr<Window>> windows;
   windows.reserve(window_layers.size());
   for (const auto& layers : window_layers) {
     if (layers.empty()) {
-      throw std::runtime_error("poa_windows_gpu: window without a backbone");
+      throw std::runtime_error(std::string(caller) + ": window without a backbone");
     }
     const auto& bb = layers.front();
     auto w = createWindow(0, 0, tgs ? WindowType::kTGS : WindowType::kNGS,
@@ -459,6 +455,22 @@ std::vector<std::pair<std::string, bool>> poa_windows_gpu(
     }
     windows.push_back(std::move(w));
   }
+  return windows;
+}
+
+// Window-level CPU-vs-GPU differ entry: runs the HIP POA kernel directly on
+// raw windows (backbone first; layer spans in backbone coordinates), so a
+// divergent window found end-to-end can be isolated and replayed. Returns
+// (consensus, polished) per window — exactly what the pipeline would store.
+// Windows the GPU cannot run (< 3 layers, overflow) return the same CPU
+// fallback semantics as HipPolisher::polish.
+std::vector<std::pair<std::string, bool>> poa_windows_gpu(
+    const std::vector<std::vector<std::tuple<std::string, std::string, uint32_t, uint32_t>>>&
+        window_layers,
+    int8_t match, int8_t mismatch, int8_t gap, bool banded, bool trim, bool tgs) {
+  std::vector<std::pair<std::string, bool>> out(window_layers.size());
+  std::vector<std::shared_ptr<Window>> windows =
+      windows_from_layers(window_layers, tgs, "poa_windows_gpu");
 
   hip::PoaBatch batch(0, 4ull << 30, match, mismatch, gap, banded, 200);
   size_t begin = 0;
@@ -499,6 +511,43 @@ std::vector<std::pair<std::string, bool>> poa_windows_gpu(
     }
   }
   flush(windows.size());
+  return out;
+}
+
+// Test and debugging entry (the polishing path does not call it): runs the
+// windows as poa_windows_gpu does, all in one batch so that each keeps a slab
+// of its own, and reads the graph back from the slabs. Per window: (status,
+// rank per node, out-edge targets per node in list order); the lists are
+// empty unless the status is kPoaOk. Refuses windows the device would not run
+// (< 3 layers, backbone too long) or that do not fit one batch.
+std::vector<std::tuple<int32_t, std::vector<uint16_t>, std::vector<std::vector<uint16_t>>>>
+poa_window_graph_gpu(const RawWindows& window_layers, int8_t match, int8_t mismatch, int8_t gap,
+                     bool banded) {
+  std::vector<std::shared_ptr<Window>> windows =
+      windows_from_layers(window_layers, true, "poa_window_graph_gpu");
+  hip::PoaBatch batch(0, 4ull << 30, match, mismatch, gap, banded, 200);
+  for (const auto& w : windows) {
+    bool never_fits = false;
+    if (w->num_layers() < 3 || !batch.add_window(w, &never_fits)) {
+      throw std::runtime_error(
+          "poa_window_graph_gpu: every window must run on the device, in one batch");
+    }
+  }
+  std::vector<std::tuple<int32_t, std::vector<uint16_t>, std::vector<std::vector<uint16_t>>>> out(
+      windows.size());
+  if (windows.empty()) {
+    return out;
+  }
+  (void)batch.generate(false);
+  for (size_t i = 0; i < windows.size(); ++i) {
+    const hip::PoaBatch::WindowGraph g = batch.read_graph(static_cast<uint32_t>(i));
+    std::vector<std::vector<uint16_t>> edges(g.rank.size());
+    for (size_t node = 0; node < edges.size(); ++node) {
+      const uint16_t* row = g.out_edges.data() + node * hip::kPoaLimits.max_edges;
+      edges[node].assign(row, row + std::min<uint32_t>(g.out_cnt[node], hip::kPoaLimits.max_edges));
+    }
+    out[i] = {g.status, g.rank, std::move(edges)};
+  }
   return out;
 }
 

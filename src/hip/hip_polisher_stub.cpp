@@ -44,6 +44,13 @@ std::vector<std::pair<std::string, bool>> poa_windows_gpu(
   fprintf(stderr, "[rga::hip::poa_windows_gpu] error: no HIP backend in this build!\n");
   exit(1);
 }
+std::vector<std::tuple<int32_t, std::vector<uint16_t>, std::vector<std::vector<uint16_t>>>>
+poa_window_graph_gpu(
+    const std::vector<std::vector<std::tuple<std::string, std::string, uint32_t, uint32_t>>>&,
+    int8_t, int8_t, int8_t, bool) {
+  fprintf(stderr, "[rga::hip::poa_window_graph_gpu] error: no HIP backend in this build!\n");
+  exit(1);
+}
 std::vector<std::tuple<std::string, int32_t, int32_t>> align_pairs(
     const std::vector<std::pair<std::string, std::string>>&, uint32_t) {
   fprintf(stderr, "[rga::hip::align_pairs] error: no HIP backend in this build!\n");

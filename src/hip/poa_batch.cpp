@@ -99,6 +99,7 @@ void PoaBatch::allocate_arenas(bool banded) {
     carve(arena_.coverage, slabs * L.max_consensus);
     carve(arena_.consensus_len, slabs);
     carve(arena_.status, slabs);
+    carve(arena_.num_nodes, slabs);
     return total;
   };
   for (;; num_slabs_ /= 2) {
@@ -297,9 +298,11 @@ std::vector<bool> PoaBatch::generate(bool trim) {
   });
   std::vector<PoaWindowDesc> desc_sorted(nw0);
   std::vector<uint32_t> lidx_sorted(nw0);
+  launch_slot_.assign(nw0, 0);
   for (uint32_t w = 0; w < nw0; ++w) {
     desc_sorted[w] = h_desc_[perm[w]];
     lidx_sorted[w] = h_layer_index_[perm[w]];
+    launch_slot_[perm[w]] = w;
   }
   std::copy(desc_sorted.begin(), desc_sorted.end(), h_desc_);
   std::copy(lidx_sorted.begin(), lidx_sorted.end(), h_layer_index_);
@@ -408,7 +411,40 @@ std::vector<bool> PoaBatch::generate(bool trim) {
   return polished;
 }
 
+PoaBatch::WindowGraph PoaBatch::read_graph(uint32_t index) const {
+  if (index >= launch_slot_.size() || launch_slot_.size() != windows_.size()) {
+    throw std::runtime_error("[rga::hip::PoaBatch] read_graph: no such window in the last run");
+  }
+  RGA_HIP_CHECK(hipSetDevice(device_));
+  WindowGraph g;
+  g.status = h_status_[launch_slot_[index]];
+  if (g.status != kPoaOk) {
+    return g;
+  }
+  uint32_t n = 0;
+  RGA_HIP_CHECK(hipMemcpy(&n, arena_.num_nodes + launch_slot_[index], sizeof(n),
+                          hipMemcpyDeviceToHost));
+  if (n > L.max_nodes) {
+    throw std::runtime_error("[rga::hip::PoaBatch] read_graph: node count beyond the slab");
+  }
+  // add_window gave window `index` the slab of the same number
+  const size_t slab = static_cast<size_t>(index) * L.max_nodes;
+  g.rank.resize(n);
+  g.out_cnt.resize(n);
+  g.out_edges.resize(static_cast<size_t>(n) * L.max_edges);
+  if (n != 0) {
+    RGA_HIP_CHECK(hipMemcpy(g.rank.data(), arena_.slabs.rank + slab, n * sizeof(uint16_t),
+                            hipMemcpyDeviceToHost));
+    RGA_HIP_CHECK(hipMemcpy(g.out_cnt.data(), arena_.slabs.out_cnt + slab, n,
+                            hipMemcpyDeviceToHost));
+    RGA_HIP_CHECK(hipMemcpy(g.out_edges.data(), arena_.slabs.out_edges + slab * L.max_edges,
+                            g.out_edges.size() * sizeof(uint16_t), hipMemcpyDeviceToHost));
+  }
+  return g;
+}
+
 void PoaBatch::reset() {
+  launch_slot_.clear();
   windows_.clear();
   seqs_added_.clear();
   pending_orders_.clear();

@@ -42,6 +42,18 @@ class PoaBatch {
   // polish status (false = needs CPU fallback or <3-layer backbone copy).
   std::vector<bool> generate(bool trim);
 
+  // Test and debugging entry, not used by the polishing path: the graph that
+  // the last generate() left in the slab of window `index` (add_window
+  // order). Every window of a batch has a slab of its own until reset().
+  // For a window that did not end with kPoaOk only the status is set.
+  struct WindowGraph {
+    int32_t status = kPoaNotRun;
+    std::vector<uint16_t> rank;       // node -> topological rank
+    std::vector<uint8_t> out_cnt;     // node -> out-degree
+    std::vector<uint16_t> out_edges;  // node * max_edges + e -> target
+  };
+  WindowGraph read_graph(uint32_t index) const;
+
   void reset();
 
  private:
@@ -80,6 +92,7 @@ class PoaBatch {
   std::vector<uint32_t> seqs_added_;  // layers shipped per window (coverage)
   std::vector<std::vector<uint32_t>> pending_orders_;  // layer order per reserved window
   size_t packed_upto_ = 0;
+  std::vector<uint32_t> launch_slot_;  // last generate(): kernel slot per window
 };
 
 }  // namespace rga::hip

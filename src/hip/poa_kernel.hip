@@ -19,9 +19,13 @@
 // LANE-PARALLEL after each topological sort, and the DP records a move byte
 // per cell so the serial traceback is one byte load per step. The graph
 // phases stay in global memory and are hidden by the deep window
-// co-residency, as in v1. Of them only the traceback and the Kahn FIFO,
-// whose order is the result, still run on lane 0: threading the path into
-// the graph (add_alignment_d) handles 64 sequence positions per step.
+// co-residency, as in v1. Threading the path into the graph
+// (add_alignment_d) handles 64 sequence positions per step. The traceback
+// and the Kahn FIFO, whose order is the result, keep that order but no
+// longer wait for global memory step by step: the traceback reads 64 moves
+// of the predicted path per round trip on all lanes (traceback_d), and the
+// FIFO core, still on lane 0, runs from an LDS copy of the adjacency
+// (topo_sort_d).
 //
 // Semantics mirror the CPU engine (src/align/poa.cpp) so GPU results are
 // deterministic and window-content-only (reference racon-gpu pins separate
@@ -110,36 +114,74 @@ __device__ inline uint64_t pack_rd(uint8_t letter, uint8_t nin, uint16_t node,
          (static_cast<uint64_t>(flags) << 48);
 }
 
+// Kahn out-adjacency word (Shared::kahn.adj): first out-edge target in the
+// low 11 bits (node ids stop at max_nodes - 1 < 2048), out-degree above it,
+// saturating at kAdjSat (a saturated word sends the FIFO to out_cnt).
+constexpr uint32_t kAdjBits = 11;
+constexpr uint32_t kAdjMask = (1u << kAdjBits) - 1;
+constexpr uint32_t kAdjSat = 31;
+static_assert(kPoaLimits.max_nodes <= kAdjMask + 1, "node id does not fit the adjacency word");
+
 // LDS block state — cross-batch window co-residency is the dominant
 // throughput lever (a 19 KB variant with full graph-array mirrors made each
-// window ~10% faster but halved residency and lost 20% end to end), so only
-// two things live here: the DP row ring, and — aliased into the same union
-// because the phases never overlap — the Kahn scratch + FIFO queue, which
-// kills the store-to-load round trip the serial sort otherwise does against
-// HBM for every node. The queue doubles as the topological order read by
-// the consensus phase. Everything else stays in the global slabs, hidden by
-// co-residency.
+// window ~10% faster but halved residency and lost 20% end to end), so the
+// block is ONE union whose sides are the phases of a layer, which never
+// overlap in time:
+//   dp    the DP row ring, the layer's match bitvectors and the staged row
+//         descriptors;
+//   tb    the traceback's first-predecessor table;
+//   kahn  the topological sort's in-degree scratch, FIFO queue and packed
+//         out-adjacency, so that the serial FIFO touches global memory only
+//         for nodes with two or more out-edges.
+// The budget is what the register-limited occupancy leaves per block, not
+// what the DP needs: 160 KiB / (4 SIMDs * min_waves) is 8 KiB for the mid
+// variant (5 waves) and 10 KiB for the others (4 waves), and the kahn side
+// (5 bytes per node of capacity) fills exactly that. Growing any side past
+// it costs residency, which is the 31 KB experiment again.
 //
-// The ring width W is a template parameter: the kernel is instantiated per
-// ring width of kPoaVariants so the ~500-column windows of a
-// default w=500 run pay ~7 KB of LDS (23 blocks/CU, ~5.7 waves/SIMD)
-// instead of the full-width 10.5 KB (15 blocks/CU, ~3.75/SIMD) — LDS, not
-// VGPRs (60), is the occupancy limiter.
+// Aliasing rules. A block is one wavefront, and its LDS accesses complete in
+// program order, so a side is dead as soon as the code that reads it is
+// behind: the barriers below only stop the compiler from moving accesses
+// across a phase boundary and make a phase's writes visible to all lanes.
+//   dp   -> tb:   pred0 is staged after the last row's trailing
+//                 wave_lds_sync; nothing of the ring is read afterwards.
+//   tb   -> kahn: traceback_d has returned, and add_alignment_d between
+//                 them uses no LDS.
+//   kahn -> dp:   match is rebuilt at the top of every layer
+//                 (build_match_bits_d, closed by __syncthreads) and rd_block
+//                 before every 64 rows (closed by wave_lds_sync); the ring
+//                 rows are written before they are read, as ever. The rank
+//                 write-back that reads the queue is closed by
+//                 __syncthreads inside topo_sort_d.
+// The queue doubles as the topological order read by consensus_d: the last
+// thing a window's layer loop runs is a topological sort, and a layer that
+// is skipped touches no LDS. Everything else stays in the global slabs,
+// hidden by co-residency.
+//
+// The ring width W and the node capacity MN are template parameters: the
+// kernel is instantiated per row of kPoaVariants.
 template <uint32_t W, uint32_t MN>
 struct alignas(16) Shared {
   union {
-    int16_t ring[kRing][W];  // DP rows (slot = row % kRing)
+    struct {
+      int16_t ring[kRing][W];  // DP rows (slot = row % kRing)
+      // per-layer match bitvectors: bit l of match[c][k] says layer base
+      // (1 + k*64 + l) equals code c — turns the per-cell seq comparison into
+      // one register bit test instead of a byte load. One spare word so
+      // cross-word extraction at the last chunk never reads out of bounds.
+      uint64_t match[4][W / 64 + 1];
+      uint64_t rd_block[64];  // row descriptors staged 64 at a time
+    } dp;
+    struct {
+      // per DP row: the row of in-edge 0's source, 0 for virtual row 0
+      uint16_t pred0[MN];
+    } tb;
     struct {
       uint8_t work[MN];    // Kahn in-degree scratch (in-degree < 256)
       uint16_t queue[MN];  // Kahn FIFO == topological order
+      uint16_t adj[MN];    // first out-edge | out-degree << kAdjBits
     } kahn;
   } u;
-  // per-layer match bitvectors: bit l of match[c][k] says layer base
-  // (1 + k*64 + l) equals code c — turns the per-cell seq comparison into
-  // one register bit test instead of a byte load. One spare word so
-  // cross-word extraction at the last chunk never reads out of bounds.
-  uint64_t match[4][W / 64 + 1];
-  uint64_t rd_block[64];  // row descriptors staged 64 at a time
 };
 
 __device__ inline int32_t poa_code(uint8_t b) {
@@ -347,30 +389,88 @@ __device__ void add_alignment_d(WindowCtx& c, const uint8_t* seq, const uint8_t*
 // Kahn topological sort (FIFO, deterministic) over the LDS mirrors. The
 // FIFO queue IS the final topological order (s.u.kahn.queue); rank goes to
 // the global slab (read lane-parallel by build_row_desc).
-// Cooperative: the in-degree staging and the rank writeback are
+// Cooperative: the staging, the queue seeding and the rank writeback are
 // lane-parallel; only the FIFO core (whose order is the deterministic
 // topological order) stays on lane 0. Call from ALL lanes.
+//
+// The FIFO's chain of dependent reads stays in LDS on the common path: the
+// staging leaves, next to the in-degrees, one word per node with its first
+// out-edge and its out-degree (Shared::kahn.adj), loaded 64 nodes at a time
+// with independent loads. A node with at most one out-edge then costs the
+// FIFO no global access at all; a node with more reads the rest of its edge
+// row eight edges per 16-byte load, and those loads do not wait for out_cnt.
+// The pop order is the serial one: sources by ascending id, then every
+// node's out-edges in list order.
 template <class SH>
 __device__ void topo_sort_d(WindowCtx& c, SH& s, int lane) {
   const uint32_t n = c.num_nodes;
-  for (uint32_t i = lane; i < n; i += kLanes) {
-    s.u.kahn.work[i] = c.in_cnt[i];
+  // staging + seeding: the sources of a 64-node block go to the queue behind
+  // those of the blocks before it, in lane (= id) order
+  uint32_t qtail = 0;
+  for (uint32_t blk = 0; blk < n; blk += kLanes) {
+    const uint32_t i = blk + lane;
+    bool source = false;
+    if (i < n) {
+      const uint32_t nin = c.in_cnt[i];
+      const uint32_t nout = c.out_cnt[i];
+      const uint32_t first = c.out_edges[i * kMaxE];  // unused when nout == 0
+      s.u.kahn.work[i] = static_cast<uint8_t>(nin);
+      s.u.kahn.adj[i] = static_cast<uint16_t>(
+          nout == 0 ? 0u : ((first & kAdjMask) | (min(nout, kAdjSat) << kAdjBits)));
+      source = nin == 0;
+    }
+    const uint64_t src_mask = __ballot(source);
+    if (source) {
+      s.u.kahn.queue[qtail + __popcll(src_mask & ((1ull << lane) - 1))] =
+          static_cast<uint16_t>(i);
+    }
+    qtail += __popcll(src_mask);
   }
   __syncthreads();
   if (lane == 0) {
-    uint32_t qhead = 0, qtail = 0;
-    for (uint32_t i = 0; i < n; ++i) {
-      if (s.u.kahn.work[i] == 0) {
-        s.u.kahn.queue[qtail++] = static_cast<uint16_t>(i);
+    constexpr uint32_t kNone = 0xffffffffu;
+    uint32_t qhead = 0;
+    // the entry at queue[qhead] when it is also the one pushed last: the
+    // next pop takes it from here (chain regions: one node in flight)
+    uint32_t fwd = kNone;
+    auto visit = [&](uint32_t v) {
+      const uint8_t left = static_cast<uint8_t>(s.u.kahn.work[v] - 1);
+      s.u.kahn.work[v] = left;
+      if (left == 0) {
+        if (qtail == qhead) {
+          fwd = v;
+        }
+        s.u.kahn.queue[qtail++] = static_cast<uint16_t>(v);
       }
-    }
+    };
     while (qhead < qtail) {
-      uint16_t u = s.u.kahn.queue[qhead++];
-      uint32_t nout = c.out_cnt[u];
-      for (uint32_t e = 0; e < nout; ++e) {
-        uint16_t v = out_edge_of(c, u, e);
-        if (--s.u.kahn.work[v] == 0) {
-          s.u.kahn.queue[qtail++] = v;
+      const uint32_t u = fwd != kNone ? fwd : s.u.kahn.queue[qhead];
+      ++qhead;
+      fwd = kNone;
+      const uint32_t word = s.u.kahn.adj[u];
+      uint32_t nout = word >> kAdjBits;
+      if (nout == 0) {
+        continue;
+      }
+      visit(word & kAdjMask);
+      if (nout == 1) {
+        continue;
+      }
+      if (nout == kAdjSat) {
+        nout = c.out_cnt[u];
+      }
+      // edge rows are 96 bytes from a 256-byte aligned base: 16-byte loads
+      static_assert(kMaxE % 8 == 0 && (kPoaLimits.max_nodes * kMaxE * 2) % 16 == 0);
+      const uint16_t* row = c.out_edges + u * kMaxE;
+      for (uint32_t base = 0; base < nout; base += 8) {
+        const uint4 v4 = *reinterpret_cast<const uint4*>(row + base);
+        const uint32_t ws[4] = {v4.x, v4.y, v4.z, v4.w};
+#pragma unroll
+        for (uint32_t k = 0; k < 8; ++k) {
+          const uint32_t e = base + k;
+          if (e != 0 && e < nout) {
+            visit((ws[k >> 1] >> ((k & 1) * 16)) & 0xffffu);
+          }
         }
       }
     }
@@ -581,7 +681,7 @@ __device__ void build_match_bits_d(SH& s, const uint8_t* seq, uint32_t len, int 
         }
       }
     }
-    s.match[cc][k] = bits;
+    s.u.dp.match[cc][k] = bits;
   }
   __syncthreads();
 }
@@ -704,7 +804,7 @@ __device__ __forceinline__ void dp_row(const WindowCtx c, SH& s, const LayerDp& 
   const bool store_row = (flags & kRdStore) != 0;
   int16_t* Hrow = c.matrix + static_cast<size_t>(r + 1) * kMaxW;
   uint8_t* Mrow = c.moves + static_cast<size_t>(r + 1) * kMaxW;
-  int16_t* ring_row = s.u.ring[(r + 1) % kRing];
+  int16_t* ring_row = s.u.dp.ring[(r + 1) % kRing];
 
   uint32_t pred_rows[kMaxPre];  // see pred_row_of
   pred_rows[0] = pred0;
@@ -747,7 +847,7 @@ __device__ __forceinline__ void dp_row(const WindowCtx c, SH& s, const LayerDp& 
       }
     }
     if (r + 1 - p < kRing) {
-      return s.u.ring[p % kRing][col];
+      return s.u.dp.ring[p % kRing][col];
     }
     return c.matrix[static_cast<size_t>(p) * kMaxW + col];
   };
@@ -807,9 +907,9 @@ __device__ __forceinline__ void dp_row(const WindowCtx c, SH& s, const LayerDp& 
     if (letter_code >= 0 && nown > 0) {
       const uint32_t bit0 = cbase & 63;
       const uint32_t w0 = cbase >> 6;
-      mbits = s.match[letter_code][w0] >> bit0;
+      mbits = s.u.dp.match[letter_code][w0] >> bit0;
       if (bit0 != 0) {
-        mbits |= s.match[letter_code][w0 + 1] << (64 - bit0);
+        mbits |= s.u.dp.match[letter_code][w0 + 1] << (64 - bit0);
       }
     } else if (nown > 0) {
       for (uint32_t w = 0; w < nown; ++w) {
@@ -866,7 +966,7 @@ __device__ __forceinline__ void dp_row(const WindowCtx c, SH& s, const LayerDp& 
           }
           if (r + 1 - p < kRing) {
             const uint32_t slot = p % kRing;
-            gather_row<WB>([&](uint32_t col) -> const int16_t& { return s.u.ring[slot][col]; },
+            gather_row<WB>([&](uint32_t col) -> const int16_t& { return s.u.dp.ring[slot][col]; },
                            cbase, MAXW - 1, okmask, pv);
           } else {
             const int16_t* gsrc = c.matrix + static_cast<size_t>(p) * kMaxW;
@@ -1035,60 +1135,161 @@ __device__ __forceinline__ void dp_row(const WindowCtx c, SH& s, const LayerDp& 
   }
 }
 
-// ---------- serial (lane 0) traceback ----------
+// ---------- traceback ----------
+
+// rounds of the traceback read this many moves of the predicted path at once
+constexpr uint32_t kTbDepth = 64;
+static_assert(kTbDepth <= kLanes, "one lane per predicted move");
 
 // Walks the move bytes back from (best_row, len) to the origin. The walk
 // ends at column 0, so it passes every sequence position exactly once:
 // aln_nodes[p] gets the node position p is aligned to, or -1 for an
 // insertion — indexed by position, which is what add_alignment_d loads 64
 // at a time. Path entries that consume a graph node only (up moves) thread
-// nothing into the graph and are not recorded.
-__device__ void traceback_d(WindowCtx& c, uint32_t best_row, uint32_t len) {
-  uint32_t i = best_row, j = len;
-  while (!(i == 0 && j == 0)) {
-    uint32_t prev_i = i, prev_j = j;
-    int32_t rec_node = -1, rec_seq = -1;
-    if (i == 0) {
-      // row 0: all-gap prefix — consume remaining columns
-      rec_seq = static_cast<int32_t>(j - 1);
-      prev_j = j - 1;
-    } else {
-      const uint8_t mv = c.moves[static_cast<size_t>(i) * kMaxW + (j != 0 ? j - 1 : kMaxW - 1)];
-      const uint8_t type = mv & 3;
-      const uint32_t e = mv >> 2;
-      const uint64_t rd = c.row_desc[i - 1];
-      const uint32_t node = static_cast<uint32_t>((rd >> 16) & 0xffff);
-      const uint32_t nin = static_cast<uint32_t>((rd >> 8) & 0xff);
-      if (type == kMvLeft) {
-        rec_seq = static_cast<int32_t>(j - 1);
-        prev_j = j - 1;
-      } else {
-        uint32_t p = 0;  // virtual row 0: genuine start rows (nin==0)
-                         // and subgraph sources (edge sentinel 63)
-        if (nin != 0 && e != 63) {
-          p = (e == 0) ? static_cast<uint32_t>((rd >> 32) & 0xffff)
-                       : c.rank[c.in_edges[node * kMaxE + e]] + 1;
-        }
-        if (type == kMvDiag) {
-          rec_node = static_cast<int32_t>(node);
-          rec_seq = static_cast<int32_t>(j - 1);
-          prev_i = p;
-          prev_j = j - 1;
-        } else if (type == kMvUp) {
-          rec_node = static_cast<int32_t>(node);
-          prev_i = p;
-        } else {
-          c.status = kPoaConsensusOverflow;  // invalid move: fail window
-          break;
-        }
-      }
-    }
-    if (rec_seq != -1) {
-      c.aln_nodes[rec_seq] = rec_node;
-    }
-    i = prev_i;
-    j = prev_j;
+// nothing into the graph and are not recorded. Call from ALL lanes.
+//
+// The move bytes fix the path; what is speculative is only when they are
+// read. The serial walk pays one global round trip per step, because the
+// address of a move depends on the move before it. Nearly all moves are
+// "diagonal through in-edge 0" (byte 0), so a round predicts that the next
+// kTbDepth moves are, and reads them all in ONE round trip:
+//   chase   from (i, j), follow pred0 (LDS, staged below from row_desc) so
+//           that lane k holds the row i_k reached after k such moves, its
+//           column being j - k; stop at virtual row 0, at column 0 and at
+//           kTbDepth;
+//   load    every lane with a position loads its move byte and its row
+//           descriptor;
+//   accept  the lanes before the first byte that is not 0 were on the path
+//           and record their node; that first lane is on the path too (its
+//           position depends only on accepted moves), and its move is taken
+//           as the serial walk takes it, all lanes in step. The next round
+//           starts where that move leads.
+// Row 0 with columns left is a run of insertions, filled lane-parallel.
+// Column 0 with rows left (the move slot at kMaxW - 1) records nothing and
+// stays a serial walk.
+//
+// pred0 holds 0 for an in-edge that the subgraph restriction cuts (source
+// row <= rlo): a row whose in-edge 0 is cut cannot carry byte 0, so no lane
+// behind it is ever accepted, and the chase ends there instead of following
+// rows that were not staged. Lanes beyond the first deviation load bytes of
+// rows rlo+1..best_row at columns below j, which are inside the slab whether
+// or not this layer wrote them, and are ignored.
+//
+// NOT inlined, on purpose. Inlined into the kernel, this function's values
+// compete for registers with the DP rows of the mid variant, which has none
+// to spare at 5 waves/SIMD: the rows gained per-row spills and 16-48
+// reloads. As a call it has a register file of its own, and the rows compile
+// as they did without it. That is why it takes what it reads by value and
+// the staging table as an LDS pointer (a reference to the window context
+// would pin the whole context in scratch memory, and a generic pointer would
+// turn the chase into flat loads, as generic slab pointers would the loads),
+// and returns the status instead of setting it. A call costs the kernels 8 bytes of stack per lane, outside
+// the rows.
+#define RGA_GLOBAL __attribute__((address_space(1)))
+struct TracebackArrays {
+  RGA_GLOBAL const uint8_t* moves;
+  RGA_GLOBAL const uint64_t* row_desc;
+  RGA_GLOBAL const uint16_t* rank;
+  RGA_GLOBAL const uint16_t* in_edges;
+  RGA_GLOBAL int32_t* aln_nodes;
+};
+using LdsU16 = __attribute__((address_space(3))) uint16_t;
+
+__device__ __attribute__((noinline)) int32_t traceback_d(const TracebackArrays c, LdsU16* pred0,
+                                                         uint32_t rlo, uint32_t best_row,
+                                                         uint32_t len, int lane) {
+  int32_t status = kPoaOk;
+  for (uint32_t r = rlo + 1 + lane; r <= best_row; r += kLanes) {
+    const uint32_t p = static_cast<uint32_t>((c.row_desc[r - 1] >> 32) & 0xffff);
+    pred0[r] = static_cast<uint16_t>(p > rlo ? p : 0);
   }
+  __syncthreads();
+
+  uint32_t i = best_row, j = len;  // wave-uniform
+  while (!(i == 0 && j == 0)) {
+    if (i == 0) {
+      // row 0: all-gap prefix — the remaining columns are insertions
+      for (uint32_t p = lane; p < j; p += kLanes) {
+        c.aln_nodes[p] = -1;
+      }
+      break;
+    }
+    uint32_t mv;
+    uint64_t rd;
+    if (j != 0) {
+      uint32_t ik = 0;    // lane k: row after k predicted moves
+      uint32_t cur = i;   // uniform chase cursor
+      uint32_t live = 0;  // lanes 0..live-1 hold a position
+      const uint32_t depth = min(kTbDepth, j);
+      while (live < depth && cur != 0) {
+        if (static_cast<uint32_t>(lane) == live) {
+          ik = cur;
+        }
+        cur = pred0[cur];
+        ++live;
+      }
+      const bool has_pos = static_cast<uint32_t>(lane) < live;
+      uint32_t mvk = 0;
+      uint64_t rdk = 0;
+      if (has_pos) {
+        mvk = c.moves[static_cast<size_t>(ik) * kMaxW + (j - lane - 1)];
+        rdk = c.row_desc[ik - 1];
+      }
+      const uint64_t dev = __ballot(has_pos && mvk != 0);
+      const uint32_t first =
+          dev != 0 ? static_cast<uint32_t>(__ffsll(static_cast<long long>(dev))) - 1 : live;
+      if (static_cast<uint32_t>(lane) < first) {
+        c.aln_nodes[j - lane - 1] = static_cast<int32_t>((rdk >> 16) & 0xffff);
+      }
+      j -= first;
+      if (first == live) {
+        i = cur;  // every predicted move held
+        continue;
+      }
+      i = __shfl(ik, static_cast<int>(first), kLanes);
+      mv = __shfl(mvk, static_cast<int>(first), kLanes);
+      const uint32_t rd_lo = __shfl(static_cast<uint32_t>(rdk), static_cast<int>(first), kLanes);
+      const uint32_t rd_hi =
+          __shfl(static_cast<uint32_t>(rdk >> 32), static_cast<int>(first), kLanes);
+      rd = (static_cast<uint64_t>(rd_hi) << 32) | rd_lo;
+    } else {
+      mv = c.moves[static_cast<size_t>(i) * kMaxW + kMaxW - 1];
+      rd = c.row_desc[i - 1];
+    }
+
+    // one move of the serial walk at (i, j), all lanes in step
+    const uint32_t type = mv & 3;
+    const uint32_t e = mv >> 2;
+    const uint32_t node = static_cast<uint32_t>((rd >> 16) & 0xffff);
+    const uint32_t nin = static_cast<uint32_t>((rd >> 8) & 0xff);
+    // a column-0 slot only ever holds an up move; anything else there, like
+    // move type 3 anywhere, is not a path: fail the window
+    if (type == 3 || (j == 0 && type != kMvUp)) {
+      status = kPoaConsensusOverflow;
+      break;
+    }
+    if (type == kMvLeft) {
+      if (lane == 0) {
+        c.aln_nodes[j - 1] = -1;
+      }
+      --j;
+      continue;
+    }
+    uint32_t p = 0;  // virtual row 0: genuine start rows (nin==0)
+                     // and subgraph sources (edge sentinel 63)
+    if (nin != 0 && e != 63) {
+      p = (e == 0) ? static_cast<uint32_t>((rd >> 32) & 0xffff)
+                   : c.rank[c.in_edges[node * kMaxE + e]] + 1;
+    }
+    if (type == kMvDiag) {
+      if (lane == 0) {
+        c.aln_nodes[j - 1] = static_cast<int32_t>(node);
+      }
+      --j;
+    }
+    i = p;
+  }
+  return status;
 }
 
 // ---------- the mega-kernel ----------
@@ -1187,12 +1388,12 @@ __global__ void poa_window_kernel(PoaDeviceArena a, uint32_t window_base,
     // moved it (measured via RGA_POA_TIMING).
     for (uint32_t rblk = d.rlo & ~(kLanes - 1); rblk <= d.rhi; rblk += kLanes) {
       if (rblk + lane < n) {
-        s.rd_block[lane] = c.row_desc[rblk + lane];
+        s.u.dp.rd_block[lane] = c.row_desc[rblk + lane];
       }
       wave_lds_sync();
       const uint32_t rlim = min(d.rhi + 1, rblk + kLanes);
       for (uint32_t r = max(rblk, d.rlo); r < rlim; ++r) {
-        dp_row<WB, MAXW>(c, s, d, r, s.rd_block[r - rblk], lane, best_score, best_row);
+        dp_row<WB, MAXW>(c, s, d, r, s.u.dp.rd_block[r - rblk], lane, best_score, best_row);
       }
       wave_lds_sync();  // rows done before the next cooperative rd_block load
     }
@@ -1200,17 +1401,27 @@ __global__ void poa_window_kernel(PoaDeviceArena a, uint32_t window_base,
     t_dp += lap();
     ++layers_done;
 
-    // ---- serial traceback on lane 0 (its order is the result) ----
-    if (lane == 0) {
-      traceback_d(c, best_row, len);
-    }
-    __syncthreads();  // lane 0's path -> visible to the whole wave
-    c.status = __shfl(c.status, 0, kLanes);
+    // The graph phases below address the slabs relative to the lane id.
+    // Those addresses do not change from layer to layer, so the compiler
+    // would compute them once per window and keep them in VGPRs across the
+    // DP rows, which have none to spare (the rows spilled): give the phases
+    // a lane id that loop-invariant code motion cannot see through.
+    int lane_g = lane;
+    asm volatile("" : "+v"(lane_g));
+
+    // ---- traceback, all lanes (the ring is dead: its LDS is reused) ----
+    c.status = traceback_d({(RGA_GLOBAL const uint8_t*)c.moves,
+                            (RGA_GLOBAL const uint64_t*)c.row_desc,
+                            (RGA_GLOBAL const uint16_t*)c.rank,
+                            (RGA_GLOBAL const uint16_t*)c.in_edges,
+                            (RGA_GLOBAL int32_t*)c.aln_nodes},
+                           (LdsU16*)s.u.tb.pred0, d.rlo, best_row, len, lane_g);
+    __syncthreads();  // the path -> visible to the whole wave
     t_tb += lap();
 
     // ---- thread the path into the graph, all lanes ----
     if (c.status == kPoaOk) {
-      add_alignment_d(c, seq, wts, len, lane);
+      add_alignment_d(c, seq, wts, len, lane_g);
     }
     // the graph updates must be visible to the whole wave
     __syncthreads();
@@ -1222,7 +1433,7 @@ __global__ void poa_window_kernel(PoaDeviceArena a, uint32_t window_base,
 
     (void)lap();
     if (c.status == kPoaOk) {
-      topo_sort_d(c, s, lane);  // cooperative (internal barriers)
+      topo_sort_d(c, s, lane_g);  // cooperative (internal barriers)
     }
     if (lane == 0) {
       t_topo += lap();
@@ -1231,7 +1442,7 @@ __global__ void poa_window_kernel(PoaDeviceArena a, uint32_t window_base,
     // rebuild the packed row descriptors for the grown graph, lane-parallel
     (void)lap();
     if (c.status == kPoaOk) {
-      build_row_desc(c, lane);
+      build_row_desc(c, lane_g);
     }
     __syncthreads();
     t_rd += lap();
@@ -1249,6 +1460,7 @@ __global__ void poa_window_kernel(PoaDeviceArena a, uint32_t window_base,
     t_cons = lap();
     a.consensus_len[win] = clen < 0 ? 0 : static_cast<uint32_t>(clen);
     a.status[win] = c.status;
+    a.num_nodes[win] = c.num_nodes;
     if (TIMED) {
       timing[0] = t_dp;
       timing[1] = t_tb;

@@ -4,8 +4,9 @@
 // src/cuda/cudabatch.cpp (BatchConfig(1023, 200, 256, ...), add_poa_group /
 // generate_poa / get_consensus contract) — re-designed for CDNA4: one 64-lane
 // wavefront per window, full-width DP rows streamed through HBM as int16,
-// graph phases in global memory (traceback and Kahn FIFO on lane 0, path
-// threading on all lanes) hidden by 16-32 co-resident windows per CU.
+// graph phases in global memory (Kahn FIFO core on lane 0 over an LDS copy of
+// the adjacency, traceback and path threading on all lanes) hidden by 16-32
+// co-resident windows per CU.
 #pragma once
 
 #include <cstddef>
@@ -215,6 +216,8 @@ struct PoaDeviceArena {
   uint16_t* coverage;       // [max_consensus] per window
   uint32_t* consensus_len;  // [1] per window
   int32_t* status;          // [1] per window
+  uint32_t* num_nodes;      // [1] per window: graph size at the end; stays on
+                            // the device unless PoaBatch::read_graph asks
 
   int8_t match, mismatch, gap;
   uint32_t band_width;  // 0 = full-width DP; else static band (reference -b:

@@ -35,6 +35,11 @@ std::vector<std::pair<std::string, bool>> poa_windows_gpu(
     const std::vector<std::vector<std::tuple<std::string, std::string, uint32_t, uint32_t>>>&
         window_layers,
     int8_t match, int8_t mismatch, int8_t gap, bool banded, bool trim, bool tgs);
+std::vector<std::tuple<int32_t, std::vector<uint16_t>, std::vector<std::vector<uint16_t>>>>
+poa_window_graph_gpu(
+    const std::vector<std::vector<std::tuple<std::string, std::string, uint32_t, uint32_t>>>&
+        window_layers,
+    int8_t match, int8_t mismatch, int8_t gap, bool banded);
 }
 
 namespace py = pybind11;
@@ -310,6 +315,18 @@ PYBIND11_MODULE(_racon, m) {
   }, py::arg("windows"), py::arg("match") = 3, py::arg("mismatch") = -5,
      py::arg("gap") = -4, py::arg("banded") = false, py::arg("trim") = true,
      py::arg("tgs") = true);
+  m.def("poa_window_graph_gpu",
+        [](const std::vector<
+               std::vector<std::tuple<std::string, std::string, uint32_t, uint32_t>>>& w,
+           int8_t match, int8_t mismatch, int8_t gap, bool banded) {
+          py::gil_scoped_release release;
+          return rga::hip::poa_window_graph_gpu(w, match, mismatch, gap, banded);
+        },
+        py::arg("windows"), py::arg("match") = 3, py::arg("mismatch") = -5, py::arg("gap") = -4,
+        py::arg("banded") = false,
+        "Test entry: the windows through the GPU POA kernel in one batch, then per window "
+        "(status, rank per node, out-edge targets per node) read back from its slab; the "
+        "lists are empty unless status is 0.");
   m.def("poa_consensus", &poa_consensus, py::arg("sequences"),
         py::arg("qualities") = std::vector<std::string>(), py::arg("match") = 5,
         py::arg("mismatch") = -4, py::arg("gap") = -8);
