@@ -15,9 +15,12 @@
 // layer bases, 9 KB -> ~16 blocks/CU): predecessor rows are LDS hits unless
 // the rank distance exceeds the ring (rare bubbles -> global matrix), the
 // per-row scalar pointer-chase (sorted -> letter/in-count/first-edge ->
-// pred rank) is replaced by one packed u64 `row_desc` per rank built
-// LANE-PARALLEL after each topological sort, and the DP records a move byte
-// per cell so the serial traceback is one byte load per step. The graph
+// pred rank) is replaced by two packed u64 words per rank (`row_desc`,
+// `row_desc2`: the row's letter, in-count, node, flags and the rows of its
+// first five predecessors) built LANE-PARALLEL after each topological sort,
+// and the DP records a move byte per cell — on rows with several
+// predecessors the chosen edge falls out of a keyed maximum — so the serial
+// traceback is one byte load per step. The graph
 // phases stay in global memory and are hidden by the deep window
 // co-residency, as in v1. Threading the path into the graph
 // (add_alignment_d) handles 64 sequence positions per step. The traceback
@@ -47,7 +50,11 @@ constexpr uint32_t kMaxN = kPoaLimits.max_nodes + 1;  // widest LDS Kahn arrays
 constexpr uint32_t kMaxE = kPoaLimits.max_edges;
 constexpr uint32_t kMaxR = kPoaLimits.max_ring;
 constexpr uint32_t kRing = 4;     // DP rows kept in LDS
-constexpr uint32_t kMaxPre = 2;   // predecessor rows precomputed per row
+constexpr uint32_t kMaxPre = 5;   // predecessor rows carried by the row descriptors
+// Minus infinity of a multi-predecessor row, whose candidates are compared as
+// (score << 6 | edge priority) keys: far below every real score (|score| <
+// 2^18 before the clamp) and still clear of overflow after the shift.
+constexpr int32_t kNegInfKeyed = -(1 << 21);
 
 // move byte encoding
 constexpr uint8_t kMvDiag = 0;
@@ -114,6 +121,13 @@ __device__ inline uint64_t pack_rd(uint8_t letter, uint8_t nin, uint16_t node,
          (static_cast<uint64_t>(flags) << 48);
 }
 
+// Second descriptor word (slab row_desc2): the DP rows of the sources of
+// in-edges 1..kMaxPre-1, 16 bits each, 0 where there is no such edge. With
+// in-edge 0's row in the first word, a row with up to kMaxPre predecessors
+// finds all their rows in two wave-uniform registers; only in-edges from
+// kMaxPre on are looked up in the graph arrays (pred_row_of).
+static_assert(kMaxPre == 5, "row_desc2 holds four 16-bit rows");
+
 // Kahn out-adjacency word (Shared::kahn.adj): first out-edge target in the
 // low 11 bits (node ids stop at max_nodes - 1 < 2048), out-degree above it,
 // saturating at kAdjSat (a saturated word sends the FIFO to out_cnt).
@@ -170,7 +184,8 @@ struct alignas(16) Shared {
       // one register bit test instead of a byte load. One spare word so
       // cross-word extraction at the last chunk never reads out of bounds.
       uint64_t match[4][W / 64 + 1];
-      uint64_t rd_block[64];  // row descriptors staged 64 at a time
+      uint64_t rd_block[64];   // row descriptors staged 64 at a time
+      uint64_t rd2_block[64];  // ... and their second words (row_desc2)
     } dp;
     struct {
       // per DP row: the row of in-edge 0's source, 0 for virtual row 0
@@ -608,6 +623,12 @@ __device__ void build_row_desc(WindowCtx& c, int lane) {
     if (nin > 0) {
       pred_row = static_cast<uint16_t>(c.rank[c.in_edges[node * kMaxE]] + 1);
     }
+    uint64_t rd2 = 0;
+    for (uint32_t e = 1; e < min(static_cast<uint32_t>(nin), kMaxPre); ++e) {
+      const uint64_t row = c.rank[c.in_edges[node * kMaxE + e]] + 1u;
+      rd2 |= row << (16 * (e - 1));
+    }
+    c.row_desc2[r] = rd2;
     const uint32_t nout = c.out_cnt[node];
     uint8_t flags = (nout == 0) ? kRdEnd : 0;
     for (uint32_t e = 0; e < nout; ++e) {
@@ -657,6 +678,7 @@ __device__ void init_backbone_d(WindowCtx& c, SH& s, int lane) {
     }
     c.row_desc[i] = pack_rd(bb_seq[i], nin, static_cast<uint16_t>(i),
                             static_cast<uint16_t>(i), flags);
+    c.row_desc2[i] = 0;  // a chain: no node has a second in-edge
   }
   c.num_nodes = bb_len;
   c.seqs_in_graph = 1;
@@ -710,12 +732,22 @@ struct LayerDp {
   uint32_t slope16;
 };
 
-// DP row (rank + 1) of in-edge e's source node; the first kMaxPre are
-// precomputed once per row, beyond that re-derived on use (nodes with that
-// many in-edges are rare).
+// DP row (rank + 1) of in-edge e's source node. The first kMaxPre come from
+// the row's two descriptor words (pred0 and rd2, both wave-uniform), so a row
+// with up to five predecessors — one row in three has more than one on noisy
+// long reads, one in ten three or more — never waits for the graph arrays.
+// From in-edge kMaxPre on the row is re-derived on use: two dependent global
+// loads, for rows with six or more in-edges (0.00 % of the DP rows in a probe
+// of the flagship's error model; BASELINE.md, "Multi-predecessor DP rows").
 __device__ __forceinline__ uint32_t pred_row_of(const WindowCtx& c, uint32_t node, uint32_t e,
-                                                const uint32_t (&pred_rows)[kMaxPre]) {
-  return (e < kMaxPre) ? pred_rows[e] : c.rank[c.in_edges[node * kMaxE + e]] + 1;
+                                                uint32_t pred0, uint64_t rd2) {
+  if (e == 0) {
+    return pred0;
+  }
+  if (e < kMaxPre) {
+    return static_cast<uint32_t>(rd2 >> (16 * (e - 1))) & 0xffffu;
+  }
+  return c.rank[c.in_edges[node * kMaxE + e]] + 1;
 }
 
 // Columns of banded DP row p that hold a value: [lo + 1, hi], plus column 0
@@ -732,10 +764,10 @@ __device__ __forceinline__ PredBand pred_band(const LayerDp& d, uint32_t p) {
 }
 
 // Gathers pv[w] = row(cbase + w), w in 0..WB, with columns outside okmask
-// set to -inf; `last` is the row's last addressable column. Loads are
-// UNCONDITIONAL with a clamped index + VALU select: per-element predication
-// compiled to one exec-branched flat_load each (generic pointer),
-// serializing the row. Called once for an LDS ring row and once for a
+// set to `neg` (the row's minus infinity); `last` is the row's last
+// addressable column. Loads are UNCONDITIONAL with a clamped index + VALU
+// select: per-element predication compiled to one exec-branched flat_load
+// each (generic pointer), serializing the row. Called once for an LDS ring row and once for a
 // global matrix row; each call must keep its address space (ds_read vs
 // global_load), and that is brittle: `row` is a functor indexing the
 // caller's own array expression, and each load is selected where it is
@@ -745,7 +777,7 @@ __device__ __forceinline__ PredBand pred_band(const LayerDp& d, uint32_t p) {
 // after touching this.
 template <uint32_t WB, class Row>
 __device__ __forceinline__ void gather_row(const Row& row, uint32_t cbase, uint32_t last,
-                                           uint32_t okmask, int32_t (&pv)[WB + 1]) {
+                                           uint32_t okmask, int32_t neg, int32_t (&pv)[WB + 1]) {
   if constexpr (WB == 8) {
     if (cbase + WB <= last) {
       // unpack a 16-byte vector load into pv[0..7] (cbase*2 is a
@@ -763,7 +795,7 @@ __device__ __forceinline__ void gather_row(const Row& row, uint32_t cbase, uint3
       pv[WB] = row(cbase + WB);
 #pragma unroll
       for (uint32_t w = 0; w <= WB; ++w) {
-        pv[w] = ((okmask >> w) & 1u) ? pv[w] : kNegInf;
+        pv[w] = ((okmask >> w) & 1u) ? pv[w] : neg;
       }
       return;
     }
@@ -772,13 +804,13 @@ __device__ __forceinline__ void gather_row(const Row& row, uint32_t cbase, uint3
 #pragma unroll
     for (uint32_t w = 0; w <= WB; ++w) {
       const int32_t val = row(cbase + w);
-      pv[w] = ((okmask >> w) & 1u) ? val : kNegInf;
+      pv[w] = ((okmask >> w) & 1u) ? val : neg;
     }
   } else {
 #pragma unroll
     for (uint32_t w = 0; w <= WB; ++w) {
       const int32_t val = row(min(cbase + w, last));
-      pv[w] = ((okmask >> w) & 1u) ? val : kNegInf;
+      pv[w] = ((okmask >> w) & 1u) ? val : neg;
     }
   }
 }
@@ -791,8 +823,18 @@ __device__ __forceinline__ void gather_row(const Row& row, uint32_t cbase, uint3
 // memory (208 B/lane on every variant).
 template <uint32_t WB, uint32_t MAXW, class SH>
 __device__ __forceinline__ void dp_row(const WindowCtx c, SH& s, const LayerDp& d, uint32_t r,
-                                       uint64_t rd, int lane, int32_t& best_score,
-                                       uint32_t& best_row) {
+                                       uint64_t rd, uint64_t rd2_lanes, int lane,
+                                       int32_t& best_score, uint32_t& best_row) {
+  // Every lane read the same two LDS words, so they are wave-uniform, but
+  // they arrive in vector registers. The second word (rows of in-edges 1..4,
+  // see pred_row_of) is only ever shifted by the wave-uniform edge index:
+  // keep it in scalar registers. The first stays where it is: with all of it
+  // scalar every variant needed 10 more VGPRs.
+  const uint64_t rd2 =
+      static_cast<uint64_t>(__builtin_amdgcn_readfirstlane(static_cast<uint32_t>(rd2_lanes))) |
+      (static_cast<uint64_t>(
+           __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(rd2_lanes >> 32)))
+       << 32);
   const uint32_t len = d.len;
   const uint8_t letter = static_cast<uint8_t>(rd);
   const int32_t letter_code = poa_code(letter);
@@ -806,13 +848,6 @@ __device__ __forceinline__ void dp_row(const WindowCtx c, SH& s, const LayerDp& 
   uint8_t* Mrow = c.moves + static_cast<size_t>(r + 1) * kMaxW;
   int16_t* ring_row = s.u.dp.ring[(r + 1) % kRing];
 
-  uint32_t pred_rows[kMaxPre];  // see pred_row_of
-  pred_rows[0] = pred0;
-  const uint32_t npre = min(nin, kMaxPre);
-  for (uint32_t e = 1; e < npre; ++e) {
-    pred_rows[e] = c.rank[c.in_edges[node * kMaxE + e]] + 1;
-  }
-
   // usable predecessor edges: in subgraph mode edges from ranks below
   // the window are cut; a row losing every predecessor becomes an NW
   // start row (virtual row 0), matching the CPU subgraph's sources.
@@ -822,7 +857,7 @@ __device__ __forceinline__ void dp_row(const WindowCtx c, SH& s, const LayerDp& 
   if (d.sub && nin != 0) {
     usable = 0;
     for (uint32_t e = 0; e < nin; ++e) {
-      if (pred_row_of(c, node, e, pred_rows) > d.rlo) {
+      if (pred_row_of(c, node, e, pred0, rd2) > d.rlo) {
         usable |= 1ull << e;
       }
     }
@@ -838,7 +873,9 @@ __device__ __forceinline__ void dp_row(const WindowCtx c, SH& s, const LayerDp& 
   // in banded mode, columns outside the predecessor's band are -inf
   auto pred_val = [&](uint32_t p, uint32_t col) -> int32_t {
     if (p == 0) {
-      return static_cast<int32_t>(col) * c.g;  // arithmetic row 0
+      // arithmetic row 0; no in-edge leads there (see the edge loop below,
+      // which has no such branch), kept because it costs nothing here
+      return static_cast<int32_t>(col) * c.g;
     }
     if (d.banded) {
       const PredBand pb = pred_band(d, p);
@@ -866,7 +903,7 @@ __device__ __forceinline__ void dp_row(const WindowCtx c, SH& s, const LayerDp& 
         if (!((usable >> e) & 1)) {
           continue;
         }
-        const int32_t hp0 = pred_val(pred_row_of(c, node, e, pred_rows), 0);
+        const int32_t hp0 = pred_val(pred_row_of(c, node, e, pred0, rd2), 0);
         if (hp0 > best0) {
           best0 = hp0;
           e0 = e;
@@ -892,8 +929,21 @@ __device__ __forceinline__ void dp_row(const WindowCtx c, SH& s, const LayerDp& 
   // chunk-serial carry chain (8 dependent LDS+scan segments per row).
   const uint32_t j0 = d.banded ? row_klo * kLanes : 0;
   const uint32_t jend = d.banded ? min(len, (row_khi + 1) * kLanes) : len;
-  int32_t carry_u = h0;  // u-space max through column j0 (h0 = -inf when
-                         // the band excludes column 0)
+  // Multi-predecessor rows take every maximum over keys (see the edge loop)
+  // and have a minus infinity of their own, kNegInfKeyed, which every value
+  // of the row that stands for "no cell" uses, so that such values compare
+  // with each other as they do on the other rows.
+  // (scalar on purpose: the flag derives from an LDS read, and everything
+  // selected by it would otherwise be computed per lane in VGPRs)
+  const bool keyed = __builtin_amdgcn_readfirstlane((nin > 1 && !vstart) ? 1 : 0) != 0;
+  const int32_t neg = keyed ? kNegInfKeyed : kNegInf;
+  // the scores as the edge loop adds them: times 64 next to keys
+  const int32_t sm = keyed ? c.m * 64 : c.m;
+  const int32_t sx = keyed ? c.x * 64 : c.x;
+  const int32_t sg = keyed ? c.g * 64 : c.g;
+  // u-space max through column j0: minus infinity when the band excludes
+  // column 0 (h0 was not computed)
+  int32_t carry_u = row_klo == 0 ? h0 : neg;
   int32_t last_col_val = kNegInf;
   int32_t pass_tail = 0;  // lane 63's last clamped value of the previous
                           // pass (the shifted store's column `base`)
@@ -919,11 +969,21 @@ __device__ __forceinline__ void dp_row(const WindowCtx c, SH& s, const LayerDp& 
       }
     }
 
-    int32_t bd[WB], bu[WB];  // best diagonal / vertical candidates
+    // Best diagonal / vertical candidates. On a row with one predecessor
+    // (two rows in three) they are scores. On a multi-predecessor row they
+    // are keys, (score << 6) | (63 - e) for in-edge e: one max picks the
+    // highest score and, among equal scores, the lowest edge index, which is
+    // the tie rule of the CPU engine's ascending edge loop, so the edge of a
+    // move byte falls out of the maximum and is never looked for afterwards.
+    // Edge indices stop at 47, so the low six bits of a real key are 16..63;
+    // 0 marks the initial value, which stands for "no candidate at or above
+    // minus infinity" and decodes to edge 0.
+    int32_t bd[WB], bu[WB];
+    const int32_t cand_init = keyed ? kNegInfKeyed * 64 : kNegInf;
 #pragma unroll
     for (uint32_t w = 0; w < WB; ++w) {
-      bd[w] = kNegInf;
-      bu[w] = kNegInf;
+      bd[w] = cand_init;
+      bu[w] = cand_init;
     }
 
     if (vstart) {
@@ -941,14 +1001,18 @@ __device__ __forceinline__ void dp_row(const WindowCtx c, SH& s, const LayerDp& 
         if (!((usable >> e) & 1)) {
           continue;
         }
-        const uint32_t p = pred_row_of(c, node, e, pred_rows);
-        int32_t pv[WB + 1];  // pred row values pv[w] = H(p, cbase + w)
-        if (p == 0) {
-#pragma unroll
-          for (uint32_t w = 0; w <= WB; ++w) {
-            pv[w] = static_cast<int32_t>(cbase + w) * c.g;
-          }
-        } else {
+        const uint32_t p = pred_row_of(c, node, e, pred0, rd2);
+        // pred row values pv[w] = H(p, cbase + w). p is a real row: an
+        // in-edge's source has a rank, so p >= 1, and the arithmetic row 0
+        // belongs to the virtual start above alone. This loop has no branch
+        // for p == 0 on purpose (it cost 8 VGPRs in every variant), while
+        // pred_val keeps its cheap one; the difference is deliberate. What
+        // keeps a zero field of rd2 out of here is the bound e < nin: fields
+        // are 0 only for in-edges the node does not have. Loosen that bound
+        // and a zero field reads ring or matrix row 0 (in bounds, but not
+        // the arithmetic row).
+        int32_t pv[WB + 1];
+        {
           PredBand pb{0, len, true};
           if (d.banded) {
             pb = pred_band(d, p);
@@ -967,20 +1031,55 @@ __device__ __forceinline__ void dp_row(const WindowCtx c, SH& s, const LayerDp& 
           if (r + 1 - p < kRing) {
             const uint32_t slot = p % kRing;
             gather_row<WB>([&](uint32_t col) -> const int16_t& { return s.u.dp.ring[slot][col]; },
-                           cbase, MAXW - 1, okmask, pv);
+                           cbase, MAXW - 1, okmask, neg, pv);
           } else {
             const int16_t* gsrc = c.matrix + static_cast<size_t>(p) * kMaxW;
             gather_row<WB>([&](uint32_t col) -> const int16_t& { return gsrc[col]; }, cbase,
-                           kMaxW - 1, okmask, pv);
+                           kMaxW - 1, okmask, neg, pv);
           }
         }
         // no nown guard: out-of-range pv entries are -inf and propagate
+        if (keyed) {
+          // key the row's values once; the scores below are scaled to match
+          // and leave the low six bits alone
+          const uint32_t pri = 63 - e;
+#pragma unroll
+          for (uint32_t w = 0; w <= WB; ++w) {
+            pv[w] = static_cast<int32_t>((static_cast<uint32_t>(pv[w]) << 6) | pri);
+          }
+        }
 #pragma unroll
         for (uint32_t w = 0; w < WB; ++w) {
-          const int32_t subst = ((mbits >> w) & 1) ? c.m : c.x;
+          const int32_t subst = ((mbits >> w) & 1) ? sm : sx;
           bd[w] = max(bd[w], pv[w] + subst);
-          bu[w] = max(bu[w], pv[w + 1] + c.g);
+          bu[w] = max(bu[w], pv[w + 1] + sg);
         }
+      }
+    }
+
+    // v[w]: the better of the two candidates; byte w of mvbase: the move
+    // byte it stands for, type | edge << 2 (diagonal on a tie). A left move
+    // replaces it below where the horizontal scan wins.
+    int32_t v[WB];
+    uint64_t mvbase = 0;
+    if (keyed) {
+#pragma unroll
+      for (uint32_t w = 0; w < WB; ++w) {
+        const int32_t sd = bd[w] >> 6, su = bu[w] >> 6;  // arithmetic shifts
+        const bool diag = sd >= su;
+        v[w] = diag ? sd : su;
+        const uint32_t low = static_cast<uint32_t>(diag ? bd[w] : bu[w]) & 63u;
+        const uint32_t edge = low != 0 ? 63u - low : 0u;
+        mvbase |= static_cast<uint64_t>((diag ? kMvDiag : kMvUp) | (edge << 2)) << (8 * w);
+      }
+    } else {
+      // one predecessor: edge 0; none: the virtual-start sentinel
+      const uint32_t edge_bits = vstart ? (63u << 2) : 0u;
+#pragma unroll
+      for (uint32_t w = 0; w < WB; ++w) {
+        const bool diag = bd[w] >= bu[w];
+        v[w] = diag ? bd[w] : bu[w];
+        mvbase |= static_cast<uint64_t>((diag ? kMvDiag : kMvUp) | edge_bits) << (8 * w);
       }
     }
 
@@ -991,7 +1090,7 @@ __device__ __forceinline__ void dp_row(const WindowCtx c, SH& s, const LayerDp& 
 #pragma unroll
     for (uint32_t w = 0; w < WB; ++w) {
       const int32_t j = static_cast<int32_t>(cbase + 1 + w);
-      const int32_t u = max(bd[w], bu[w]) - j * c.g;
+      const int32_t u = v[w] - j * c.g;
       run = max(run, u);
       us[w] = run;
     }
@@ -1004,58 +1103,33 @@ __device__ __forceinline__ void dp_row(const WindowCtx c, SH& s, const LayerDp& 
     carry_u = max(carry_u, __builtin_amdgcn_readlane(incl, kLanes - 1));
 
     // finalize own columns: h, moves, stores. h is computed for every
-    // slot (junk past the row end feeds only junk columns); the move
-    // logic stays guarded.
+    // slot (junk past the row end feeds only junk columns); no memory is
+    // read here.
     int32_t h_sel = kNegInf;
     uint64_t mvpack = 0;  // 8 move bytes -> one aligned store at Mrow[cbase]
     int32_t harr[WB];
 #pragma unroll
     for (uint32_t w = 0; w < WB; ++w) {
       const uint32_t j = cbase + 1 + w;
-      const int32_t v = max(bd[w], bu[w]);
       const int32_t h = max(us[w], excl) + static_cast<int32_t>(j) * c.g;
       harr[w] = h < -28000 ? -28000 : h;
-      if (w < nown) {
-        uint8_t mv;
-        if (h != v) {
-          mv = kMvLeft;
-        } else if (vstart) {
-          mv = static_cast<uint8_t>(((bd[w] >= bu[w]) ? kMvDiag : kMvUp) | (63u << 2));
-        } else if (nin == 1) {
-          mv = (bd[w] >= bu[w]) ? kMvDiag : kMvUp;
-        } else {
-          // rare multi-pred row: recover the argmax edge (first e wins)
-          const uint8_t type = (bd[w] >= bu[w]) ? kMvDiag : kMvUp;
-          const int32_t want = (type == kMvDiag) ? bd[w] : bu[w];
-          uint32_t esel = 0;
-          const int32_t subst = ((mbits >> w) & 1) ? c.m : c.x;
-          for (uint32_t e = 0; e < nin; ++e) {
-            if (!((usable >> e) & 1)) {
-              continue;
-            }
-            const uint32_t p = pred_row_of(c, node, e, pred_rows);
-            const int32_t cand =
-                (type == kMvDiag) ? pred_val(p, j - 1) + subst : pred_val(p, j) + c.g;
-            if (cand == want) {
-              esel = e;
-              break;
-            }
-          }
-          mv = static_cast<uint8_t>(type | (esel << 2));
+      const uint32_t mv =
+          (h != v[w]) ? kMvLeft : static_cast<uint32_t>(mvbase >> (8 * w)) & 0xffu;
+      if (WB == 8) {
+        mvpack |= static_cast<uint64_t>(mv) << (8 * w);  // bytes past nown: cleared below
+      } else if (w < nown) {
+        if (store_row) {
+          Hrow[j] = static_cast<int16_t>(harr[w]);
         }
-        if (WB == 8) {
-          mvpack |= static_cast<uint64_t>(mv) << (8 * w);
-        } else {
-          if (store_row) {
-            Hrow[j] = static_cast<int16_t>(harr[w]);
-          }
-          ring_row[j] = static_cast<int16_t>(harr[w]);
-          Mrow[j - 1] = mv;  // shifted layout, per-byte for odd widths
-        }
-        if (j == len) {
-          h_sel = h;
-        }
+        ring_row[j] = static_cast<int16_t>(harr[w]);
+        Mrow[j - 1] = static_cast<uint8_t>(mv);  // shifted layout, per-byte for odd widths
       }
+      if (w < nown && j == len) {
+        h_sel = h;
+      }
+    }
+    if (WB == 8 && nown < WB) {
+      mvpack &= (1ull << (8 * nown)) - 1;  // columns past the row end carry byte 0
     }
     if (WB == 8) {
       // Shifted 16-byte row stores: lane l writes columns
@@ -1389,11 +1463,13 @@ __global__ void poa_window_kernel(PoaDeviceArena a, uint32_t window_base,
     for (uint32_t rblk = d.rlo & ~(kLanes - 1); rblk <= d.rhi; rblk += kLanes) {
       if (rblk + lane < n) {
         s.u.dp.rd_block[lane] = c.row_desc[rblk + lane];
+        s.u.dp.rd2_block[lane] = c.row_desc2[rblk + lane];
       }
       wave_lds_sync();
       const uint32_t rlim = min(d.rhi + 1, rblk + kLanes);
       for (uint32_t r = max(rblk, d.rlo); r < rlim; ++r) {
-        dp_row<WB, MAXW>(c, s, d, r, s.u.dp.rd_block[r - rblk], lane, best_score, best_row);
+        dp_row<WB, MAXW>(c, s, d, r, s.u.dp.rd_block[r - rblk], s.u.dp.rd2_block[r - rblk], lane,
+                         best_score, best_row);
       }
       wave_lds_sync();  // rows done before the next cooperative rd_block load
     }

@@ -138,6 +138,10 @@ struct PoaWindowDesc {
 //             bits 2-7 in-edge index of the chosen predecessor
 //   row_desc  per-rank packed row descriptor, built lane-parallel after each
 //             topo sort: letter(8) | nin(8) | node(16) | pred_row(16) | flags(8)
+//   row_desc2 per-rank second descriptor word, built in the same pass: the DP
+//             rows (rank + 1) of the sources of in-edges 1, 2, 3 and 4, 16
+//             bits each, 0 where the node has no such edge (a predecessor's
+//             row is never 0)
 #define RGA_POA_SLAB_ARRAYS(X)                   \
   X(uint8_t, letters, N)                         \
   X(uint8_t, in_cnt, N)                          \
@@ -155,7 +159,8 @@ struct PoaWindowDesc {
   X(int32_t, aln_seq, 2 * L.matrix_width + N)    \
   X(int16_t, matrix, (N + 1) * L.matrix_width)   \
   X(uint8_t, moves, (N + 1) * L.matrix_width)    \
-  X(uint64_t, row_desc, N)
+  X(uint64_t, row_desc, N)                       \
+  X(uint64_t, row_desc2, N)
 
 struct PoaSlabs {
 #define RGA_X(T, name, count) T* name;
@@ -183,7 +188,7 @@ constexpr size_t poa_slab_bytes() {
   for_each_poa_slab(s, [&b](auto* p, size_t count) { b += count * sizeof(*p); });
   return b;
 }
-static_assert(poa_slab_bytes() == 7184020, "slab layout changed: batch sizes move with it");
+static_assert(poa_slab_bytes() == 7200396, "slab layout changed: batch sizes move with it");
 
 // Device arena pointers (one allocation, carved into slabs).
 struct PoaDeviceArena {
