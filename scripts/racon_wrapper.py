@@ -7,7 +7,8 @@ Capability parity with the reference wrapper
 with concatenated stdout. Two deliberate improvements over the reference:
 
 * GPU flags (-c/--cudapoa-batches, --cudaaligner-batches,
-  -b/--cuda-banded-alignment, --cudaaligner-band-width) are ACTUALLY
+  -b/--cuda-banded-alignment, --cudaaligner-band-width,
+  --aligner-adaptive-band) are ACTUALLY
   forwarded to racon; the reference parses but drops them
   (racon_wrapper.py:38-40,130-131 are commented out there).
 * binaries are located at runtime (RACON_BIN / RAMPLER_BIN env vars, then
@@ -78,6 +79,9 @@ def main():
                         help="banded approximation for GPU POA alignment")
     parser.add_argument("--cudaaligner-band-width", default=0,
                         help="band width for GPU alignment (0 = auto)")
+    parser.add_argument("--aligner-adaptive-band", action="store_true",
+                        help="second GPU pass, with an adaptive band, over overlaps "
+                             "that escape the alignment band")
     parser.add_argument("--in-process", action="store_true",
                         help="polish every --split chunk inside ONE process via the "
                              "_racon module instead of one racon subprocess per chunk: "
@@ -143,7 +147,8 @@ def main():
                     banded_poa=args.cuda_banded_alignment,
                     aligner_batches=int(args.cudaaligner_batches),
                     aligner_band_width=int(args.cudaaligner_band_width),
-                    include_unpolished=args.include_unpolished)
+                    include_unpolished=args.include_unpolished,
+                    aligner_adaptive_band=args.aligner_adaptive_band)
                 for name, seq in out:
                     sys.stdout.write(f">{name}\n{seq}\n")
                 sys.stdout.flush()
@@ -167,6 +172,8 @@ def main():
             cmd += ["--cudaaligner-batches", str(args.cudaaligner_batches)]
         if int(args.cudaaligner_band_width):
             cmd += ["--cudaaligner-band-width", str(args.cudaaligner_band_width)]
+        if args.aligner_adaptive_band:
+            cmd.append("--aligner-adaptive-band")
         cmd += [sequences, overlaps, None]
 
         for chunk in chunks:

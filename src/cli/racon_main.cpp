@@ -16,6 +16,7 @@ namespace {
 
 constexpr int32_t kAlignerBatchesOpt = 10000;
 constexpr int32_t kAlignerBandWidthOpt = 10001;
+constexpr int32_t kAlignerAdaptiveBandOpt = 10002;
 
 struct option long_options[] = {
     {"include-unpolished", no_argument, nullptr, 'u'},
@@ -34,6 +35,7 @@ struct option long_options[] = {
     {"cuda-banded-alignment", no_argument, nullptr, 'b'},
     {"cudaaligner-batches", required_argument, nullptr, kAlignerBatchesOpt},
     {"cudaaligner-band-width", required_argument, nullptr, kAlignerBandWidthOpt},
+    {"aligner-adaptive-band", no_argument, nullptr, kAlignerAdaptiveBandOpt},
     {nullptr, 0, nullptr, 0}};
 
 void help() {
@@ -95,7 +97,11 @@ void help() {
       "        --cudaaligner-band-width <int>\n"
       "            default: 0\n"
       "            Band width for HIP alignment. Must be >= 0. Non-zero allows user defined \n"
-      "            band width, whereas 0 implies auto band width determination.\n");
+      "            band width, whereas 0 implies auto band width determination.\n"
+      "        --aligner-adaptive-band\n"
+      "            give overlaps that escape the alignment band a second pass on the\n"
+      "            GPU, with a band that follows the scores, before the CPU aligner\n"
+      "            takes them (no effect without --cudaaligner-batches)\n");
 }
 
 }  // namespace
@@ -133,6 +139,7 @@ int main(int argc, char** argv) {
       case 'b': config.banded_poa = true; break;
       case kAlignerBatchesOpt: config.aligner_batches = atoi(optarg); break;
       case kAlignerBandWidthOpt: config.aligner_band_width = atoi(optarg); break;
+      case kAlignerAdaptiveBandOpt: config.aligner_adaptive_band = true; break;
       default: exit(1);
     }
   }

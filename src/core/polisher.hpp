@@ -45,6 +45,10 @@ struct PolisherConfig {
   bool banded_poa = false;
   uint32_t aligner_batches = 0;
   uint32_t aligner_band_width = 0;
+  // second chance for overlaps that escape the aligner band: an adaptive-band
+  // pass at the same width before the CPU aligner takes them (HIP aligner
+  // batches only)
+  bool aligner_adaptive_band = false;
 };
 
 class Polisher {

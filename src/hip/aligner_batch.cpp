@@ -10,6 +10,7 @@
 #include <thread>
 #include <vector>
 
+#include "hip/aligner_plan.hpp"
 #include "hip/hip_common.hpp"
 
 namespace rga::hip {
@@ -90,8 +91,19 @@ void AlignerBatch::allocate_arenas(size_t mem_budget) {
     const size_t fixed = 2 * seq_cap_ + peq_cap_u64_ * 8 + bp_cap_ * sizeof(AlnBpRecord) +
                          max_alignments_ * (sizeof(AlnDesc) + 16) + (2u << 20);
     const size_t state = pool > fixed ? pool - fixed : (16u << 20);
-    tb_cap_u64_ = state / 20 * 16 / 8;  // 16/20 of state bytes as u64
-    s_cap_i32_ = state / 20 * 4 / 4;    // 4/20 of state bytes as i32
+    // Per column and block: 16 B of Pv/Mv and 4 B of score, plus 4 B per
+    // column for the adaptive kernel's band top (aln_s_stride). The policy is
+    // chosen per run, so the split is always the adaptive one: both arenas
+    // then hold the same number of columns under either policy, and
+    // reserve_span can count tb words alone.
+    const size_t per_col = 16 * band_k_ + 4 * aln_s_stride(band_k_, true);
+    const size_t cols = state / per_col;  // wave-lane columns of state
+    tb_cap_u64_ = cols * band_k_ * 2;
+    s_cap_i32_ = cols * aln_s_stride(band_k_, true);
+    // The per-fill cap (reserve_span) is a load-balancing knob, not a
+    // capacity: it stays at the value the flagship was tuned with, half of a
+    // 16 : 4 split's tb arena, whatever the carve above gives the arenas.
+    fill_cap_u64_ = state / 20 * 16 / 8 / 2;
 
     // sized for the SMALLEST lanes-per-wave the launcher may pick (16 for
     // small jobs), not kLanes — and the per-sub-launch descriptor slices
@@ -200,13 +212,14 @@ int32_t AlignerBatch::reserve_span(const char* q, uint32_t q_len, const char* t,
   const size_t bytes = static_cast<size_t>(q_len) + t_len;
   // per-lane share of the wave's tb region (the wave total is 64 of these,
   // and the arena-capacity check is against the sum of all shares). The
-  // per-fill cap is HALF a tb arena: a greedy first fill at the full cap
-  // would swallow most of the overlap queue and starve the other batch
+  // per-fill cap is about HALF a tb arena: a greedy first fill at the full
+  // cap would swallow most of the overlap queue and starve the other batch
   // threads (the pull model balances only when rounds are smaller than
-  // queue/threads).
+  // queue/threads). Counting tb words covers the score arena under either
+  // band policy: the two are carved in proportion (allocate_arenas).
   const uint64_t tb_need = static_cast<uint64_t>(t_len + 1) * band_k_ * 2;
   if (overlaps_.size() >= max_alignments_ || seq_bytes_ + bytes > seq_cap_ ||
-      path_bytes_ + bytes > path_cap_ || tb_reserved_ + tb_need > tb_cap_u64_ / 2 ||
+      path_bytes_ + bytes > path_cap_ || tb_reserved_ + tb_need > fill_cap_u64_ ||
       bp_records_ + bp_need > bp_cap_) {
     return -1;
   }
@@ -285,7 +298,69 @@ void AlignerBatch::pack() {
   }
 }
 
+void AlignerBatch::launch_pass(std::vector<uint32_t> order, bool adaptive,
+                               std::vector<uint32_t>* never_run) {
+  auto s = static_cast<hipStream_t>(stream_);
+  const uint32_t count = static_cast<uint32_t>(order.size());
+  // sort into waves by descending target length (uniform per-wave loops)
+  aln_sort_for_launch(h_descs_, &order);
+  std::copy(order.begin(), order.end(), h_order_);
+  RGA_HIP_CHECK(hipMemcpyAsync(d_order_, h_order_, count * 4, hipMemcpyHostToDevice, s));
+
+  // greedy sub-launches bounded by the tb/s/peq arenas. Waves are
+  // deliberately under-filled for small jobs: at 64 alignments/wave a
+  // typical polish run yields ~1.5 waves per CU and every gather latency
+  // lands on the wall clock; 16-32/wave gives each CU interleavable waves
+  // at the cost of idle lanes (which issue no extra instructions).
+  // tuning override (RGA_ALN_LANES in {16,32,64}): alignments packed per
+  // 64-lane wave — fewer per wave = more interleavable waves per CU at the
+  // cost of idle lanes
+  static const long lanes_env = [] {
+    const char* e = getenv("RGA_ALN_LANES");
+    return e != nullptr ? atol(e) : 0;
+  }();
+  const uint32_t lanes = aln_lanes_per_wave(count, lanes_env);
+  const AlnLaunchPlan plan =
+      aln_plan_launches(h_descs_, h_order_, count, lanes, band_k_,
+                        aln_s_stride(band_k_, adaptive), {peq_cap_u64_, tb_cap_u64_, s_cap_i32_});
+  never_run->insert(never_run->end(), plan.never_run.begin(), plan.never_run.end());
+  if (plan.launches.empty()) {
+    return;
+  }
+  // every sub-launch has its own slice of the descriptor array, so they
+  // enqueue back-to-back with no intervening stream sync
+  std::copy(plan.waves.begin(), plan.waves.end(), h_waves_);
+  RGA_HIP_CHECK(hipMemcpyAsync(d_waves_, h_waves_, plan.waves.size() * sizeof(AlnWaveDesc),
+                               hipMemcpyHostToDevice, s));
+  for (const AlnSubLaunch& l : plan.launches) {
+    AlnDeviceArena launch_arena = arena_;
+    launch_arena.order = d_order_ + static_cast<size_t>(l.first_wave) * lanes;
+    launch_arena.waves = d_waves_ + l.desc_off;
+    launch_arena.lanes_per_wave = lanes;
+    launch_arena.window_length = window_length_;
+    launch_aligner_kernel(launch_arena, l.num_waves, l.num_align, band_k_, window_length_ == 0,
+                          adaptive, stream_);
+  }
+}
+
+void AlignerBatch::read_back() {
+  auto s = static_cast<hipStream_t>(stream_);
+  const uint32_t na = static_cast<uint32_t>(overlaps_.size());
+  if (window_length_ == 0) {
+    RGA_HIP_CHECK(hipMemcpyAsync(h_path_, arena_.path, path_bytes_, hipMemcpyDeviceToHost, s));
+    RGA_HIP_CHECK(
+        hipMemcpyAsync(h_path_len_, arena_.path_len, na * 4, hipMemcpyDeviceToHost, s));
+  } else {
+    RGA_HIP_CHECK(hipMemcpyAsync(h_bp_, arena_.bp, bp_records_ * sizeof(AlnBpRecord),
+                                 hipMemcpyDeviceToHost, s));
+  }
+  RGA_HIP_CHECK(hipMemcpyAsync(h_status_, arena_.status, na * 4, hipMemcpyDeviceToHost, s));
+  RGA_HIP_CHECK(hipMemcpyAsync(h_edit_, arena_.edit_distance, na * 4, hipMemcpyDeviceToHost, s));
+  RGA_HIP_CHECK(hipStreamSynchronize(s));
+}
+
 void AlignerBatch::run() {
+  retry_completed_ = 0;
   if (overlaps_.empty()) {
     return;
   }
@@ -298,133 +373,46 @@ void AlignerBatch::run() {
   RGA_HIP_CHECK(hipMemcpyAsync(const_cast<AlnDesc*>(arena_.descs), h_descs_,
                                na * sizeof(AlnDesc), hipMemcpyHostToDevice, s));
 
-  // sort into waves by descending target length (uniform per-wave loops)
-  std::vector<uint32_t> order(na);
-  std::iota(order.begin(), order.end(), 0u);
-  std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
-    if (h_descs_[x].t_len != h_descs_[y].t_len) return h_descs_[x].t_len > h_descs_[y].t_len;
-    return x < y;
-  });
-  std::copy(order.begin(), order.end(), h_order_);
-  RGA_HIP_CHECK(hipMemcpyAsync(d_order_, h_order_, na * 4, hipMemcpyHostToDevice, s));
-
-  // greedy sub-launches bounded by the tb/s/peq arenas. Waves are
-  // deliberately under-filled for small jobs: at 64 alignments/wave a
-  // typical polish run yields ~1.5 waves per CU and every gather latency
-  // lands on the wall clock; 16-32/wave gives each CU interleavable waves
-  // at the cost of idle lanes (which issue no extra instructions).
-  const uint32_t K = band_k_;
-  const bool emit_path = window_length_ == 0;
-  // Full 64-lane packing for big jobs; small jobs still under-fill waves so
-  // every CU gets interleavable work. (The 32-lane middle tier predated the
-  // back-to-back sub-launch pipeline; measured post-pipeline, 64 wins at
-  // the flagship size: 6.00 vs 5.89 Mbp/s.)
-  uint32_t lanes = kLanes;
-  if (na < 16384) {
-    lanes = 16;
-  }
-  // tuning override (RGA_ALN_LANES in {16,32,64}): alignments packed per
-  // 64-lane wave — fewer per wave = more interleavable waves per CU at the
-  // cost of idle lanes
-  static const long lanes_env = [] {
-    const char* e = getenv("RGA_ALN_LANES");
-    return e != nullptr ? atol(e) : 0;
-  }();
-  if (lanes_env == 16 || lanes_env == 32 || lanes_env == 64) {
-    lanes = static_cast<uint32_t>(lanes_env);
-  }
-  uint32_t wave_begin = 0;  // in wave units
-  uint32_t wave_desc_off = 0;  // h_waves_/d_waves_ slice per sub-launch, so
-                               // sub-launches enqueue back-to-back with no
-                               // intervening stream sync
-  const uint32_t num_waves_total = (na + lanes - 1) / lanes;
+  std::vector<uint32_t> all(na);
+  std::iota(all.begin(), all.end(), 0u);
   std::vector<uint32_t> never_run;  // original indices of un-runnable waves
-  auto wave_needs = [&](uint32_t w, uint64_t* peq_need, uint64_t* tb_need,
-                        uint64_t* s_need) {
-    uint32_t nb = K, mmax = 0;
-    for (uint32_t l = 0; l < lanes; ++l) {
-      const uint32_t slot = w * lanes + l;
-      if (slot >= na) break;
-      const AlnDesc& d = h_descs_[h_order_[slot]];
-      nb = std::max(nb, (d.q_len + 63) / 64);
-      mmax = std::max(mmax, d.t_len);
+  launch_pass(std::move(all), policy_ == AlnBandPolicy::kAdaptive, &never_run);
+  read_back();
+  // the device never wrote these alignments' results
+  auto mark_never_run = [&] {
+    for (uint32_t orig : never_run) {
+      h_status_[orig] = kAlnNotRun;
+      h_path_len_[orig] = 0;
+      h_edit_[orig] = -1;
     }
-    *peq_need = static_cast<uint64_t>(nb) * 4 * kLanes;
-    *tb_need = static_cast<uint64_t>(mmax + 1) * K * 2 * kLanes;
-    *s_need = static_cast<uint64_t>(mmax + 1) * K * kLanes;
-    return std::make_pair(nb, mmax);
   };
-  while (wave_begin < num_waves_total) {
-    // a wave whose state alone exceeds an arena (giant target at a wide
-    // explicit band: e.g. 262 kbp at K=16 needs ~4.3 GB of tb) can never
-    // launch — fail its alignments to the CPU pairwise fallback instead of
-    // writing out of bounds. No construction-time carve guarantees a full
-    // max_len wave fits; this check is the guarantee.
-    {
-      uint64_t peq_need, tb_need, s_need;
-      wave_needs(wave_begin, &peq_need, &tb_need, &s_need);
-      if (peq_need > peq_cap_u64_ || tb_need > tb_cap_u64_ || s_need > s_cap_i32_) {
-        for (uint32_t l = 0; l < lanes; ++l) {
-          const uint32_t slot = wave_begin * lanes + l;
-          if (slot >= na) break;
-          never_run.push_back(h_order_[slot]);
-        }
-        ++wave_begin;
-        continue;
-      }
-    }
-    uint64_t peq_off = 0, tb_off = 0, s_off = 0;
-    uint32_t w = wave_begin;
-    uint32_t launch_waves = 0;
-    for (; w < num_waves_total; ++w) {
-      uint64_t peq_need, tb_need, s_need;
-      auto nbm = wave_needs(w, &peq_need, &tb_need, &s_need);
-      if (launch_waves > 0 && (peq_off + peq_need > peq_cap_u64_ ||
-                               tb_off + tb_need > tb_cap_u64_ || s_off + s_need > s_cap_i32_)) {
-        break;
-      }
-      AlnWaveDesc wd;
-      wd.peq_off = peq_off;
-      wd.tb_off = tb_off;
-      wd.s_off = s_off;
-      wd.nb = nbm.first;
-      wd.mmax = nbm.second;
-      h_waves_[wave_desc_off + launch_waves] = wd;
-      peq_off += peq_need;
-      tb_off += tb_need;
-      s_off += s_need;
-      ++launch_waves;
-    }
-    const uint32_t launch_align =
-        std::min(na - wave_begin * lanes, launch_waves * lanes);
-    RGA_HIP_CHECK(hipMemcpyAsync(d_waves_ + wave_desc_off, h_waves_ + wave_desc_off,
-                                 launch_waves * sizeof(AlnWaveDesc),
-                                 hipMemcpyHostToDevice, s));
-    AlnDeviceArena launch_arena = arena_;
-    launch_arena.order = d_order_ + wave_begin * lanes;
-    launch_arena.waves = d_waves_ + wave_desc_off;
-    launch_arena.lanes_per_wave = lanes;
-    launch_arena.window_length = window_length_;
-    launch_aligner_kernel(launch_arena, launch_waves, launch_align, K, emit_path, stream_);
-    wave_begin += launch_waves;
-    wave_desc_off += launch_waves;
+  mark_never_run();
+  if (policy_ != AlnBandPolicy::kRetry) {
+    return;
   }
 
-  if (emit_path) {
-    RGA_HIP_CHECK(hipMemcpyAsync(h_path_, arena_.path, path_bytes_, hipMemcpyDeviceToHost, s));
-    RGA_HIP_CHECK(
-        hipMemcpyAsync(h_path_len_, arena_.path_len, na * 4, hipMemcpyDeviceToHost, s));
-  } else {
-    RGA_HIP_CHECK(hipMemcpyAsync(h_bp_, arena_.bp, bp_records_ * sizeof(AlnBpRecord),
-                                 hipMemcpyDeviceToHost, s));
+  // second chance: the adaptive band at the same K over the escaped
+  // alignments only, on the arena as packed. The kernel writes results of
+  // the alignments it runs and of no other, so the device still holds the
+  // first pass's for the rest and the second read-back returns them as
+  // they were.
+  std::vector<uint32_t> escaped;
+  for (uint32_t i = 0; i < na; ++i) {
+    if (h_status_[i] == kAlnBandEdge) {
+      escaped.push_back(i);
+    }
   }
-  RGA_HIP_CHECK(hipMemcpyAsync(h_status_, arena_.status, na * 4, hipMemcpyDeviceToHost, s));
-  RGA_HIP_CHECK(hipMemcpyAsync(h_edit_, arena_.edit_distance, na * 4, hipMemcpyDeviceToHost, s));
-  RGA_HIP_CHECK(hipStreamSynchronize(s));
-  for (uint32_t orig : never_run) {
-    h_status_[orig] = kAlnNotRun;
-    h_path_len_[orig] = 0;
-    h_edit_[orig] = -1;
+  if (escaped.empty()) {
+    return;
+  }
+  // a wave the adaptive pass cannot launch leaves its alignments as the
+  // first pass reported them (kAlnBandEdge)
+  std::vector<uint32_t> not_retried;
+  launch_pass(escaped, true, &not_retried);
+  read_back();
+  mark_never_run();
+  for (uint32_t i : escaped) {
+    retry_completed_ += h_status_[i] == kAlnOk ? 1 : 0;
   }
 }
 
@@ -477,11 +465,17 @@ std::vector<std::pair<uint32_t, uint32_t>> AlignerBatch::breaking_points_of(
   return points;
 }
 
-uint32_t AlignerBatch::align_and_emit(uint32_t window_length) {
+uint32_t AlignerBatch::align_and_emit(uint32_t window_length, uint32_t* adaptive_completed) {
+  if (adaptive_completed != nullptr) {
+    *adaptive_completed = 0;
+  }
   if (overlaps_.empty()) {
     return 0;
   }
   run();
+  if (adaptive_completed != nullptr) {
+    *adaptive_completed = retry_completed_;
+  }
   if (window_length_ > 0) {
     // breaking-point mode: a few records per overlap, nothing worth threads.
     // An overlap without a single matched window stays untouched, as it

@@ -53,9 +53,20 @@ class AlignerBatch {
                        bool scan_non_acgt = true, uint32_t window_length = 0,
                        uint32_t t_origin = 0, uint32_t q_origin = 0);
 
+  // Where the band lies for the runs that follow (AlnBandPolicy; diagonal
+  // unless set). A property of the use, not of the batch: pooled batches are
+  // keyed by device and band only, so whoever takes one sets the policy.
+  void set_band_policy(AlnBandPolicy policy) { policy_ = policy; }
+  AlnBandPolicy band_policy() const { return policy_; }
+
   // Runs the kernel over everything reserved (pack + sub-launches + D2H). In
   // breaking-point mode the records come back instead of path / path_len.
+  // Under kRetry a second, adaptive pass runs over the alignments the
+  // diagonal pass returned as kAlnBandEdge; every other alignment keeps its
+  // first-pass result, and kAlnNotRun alignments are not retried.
   void run();
+  // Alignments the last run()'s second pass completed (kRetry only).
+  uint32_t retry_completed() const { return retry_completed_; }
   // Post-run accessors per slot.
   int32_t status_of(uint32_t slot) const { return h_status_[slot]; }
   int32_t edit_distance_of(uint32_t slot) const { return h_edit_[slot]; }
@@ -78,15 +89,22 @@ class AlignerBatch {
   // path mode get a CIGAR string, which window_length > 0 then walks into
   // breaking points right on the emit threads — the walk overlaps the other
   // batches' kernels instead of serializing in the post-GPU CPU pass.
-  // Returns how many overlaps fell back (band-edge -> CPU aligner).
-  uint32_t align_and_emit(uint32_t window_length = 0);
+  // Returns how many overlaps fell back (band-edge -> CPU aligner); under
+  // kRetry that is the count after the second pass, and *adaptive_completed
+  // (when given) gets the number of overlaps the second pass completed.
+  uint32_t align_and_emit(uint32_t window_length = 0, uint32_t* adaptive_completed = nullptr);
 
   void reset();
 
  private:
   void allocate_arenas(size_t mem_budget);
   void release_all();
-
+  // One kernel pass over the alignments in `order` (any order; sorted here):
+  // plans the sub-launches and enqueues them. Alignments of waves that can
+  // never launch are appended to *never_run.
+  void launch_pass(std::vector<uint32_t> order, bool adaptive, std::vector<uint32_t>* never_run);
+  // D2H of the products and statuses, then a stream sync.
+  void read_back();
 
  private:
   int device_;
@@ -97,6 +115,7 @@ class AlignerBatch {
   size_t seq_cap_, path_cap_;
   size_t bp_cap_;  // window records
   uint64_t tb_cap_u64_, s_cap_i32_, peq_cap_u64_;
+  uint64_t fill_cap_u64_;  // tb words one fill may reserve
   uint32_t max_alignments_;
 
   uint8_t* h_seqs_ = nullptr;
@@ -119,6 +138,8 @@ class AlignerBatch {
   uint64_t tb_reserved_ = 0;  // u64 units of per-column state reserved
   size_t bp_records_ = 0;     // window records reserved
   uint32_t window_length_ = 0;  // of the current fill; 0 = path mode
+  AlnBandPolicy policy_ = AlnBandPolicy::kDiagonal;
+  uint32_t retry_completed_ = 0;
   std::vector<Overlap*> overlaps_;
   struct PendingSpan {
     const char* q;

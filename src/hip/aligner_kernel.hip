@@ -2,7 +2,8 @@
 //
 // Each lane runs the blocked Myers edit-distance recurrence (Myers 1999,
 // Hyyro 2003 block form) over a band of K 64-row blocks that slides along
-// the rectangle diagonal — 64 DP cells per 64-bit VALU op, no cross-lane
+// the rectangle diagonal (or, in the adaptive instantiations, follows the
+// scores downwards) — 64 DP cells per 64-bit VALU op, no cross-lane
 // communication in the hot loop (the previous anti-diagonal design spent
 // ~85 cycles per cell on ds_bpermute shuffles; this one spends ~0.5).
 // Column state (Pv/Mv per block + block-bottom scores) is stored
@@ -55,9 +56,19 @@ __device__ inline int32_t score_at(int32_t S, uint64_t Pv, uint64_t Mv, uint32_t
 // moves in the same order; path mode stores one op byte per move, while
 // breaking-point mode keeps the current window's record in registers and
 // stores it (one 16-byte write) when the walk leaves the window.
-template <int K, bool kEmitPath>
+//
+// kAdaptive selects the band policy. Off: the band top of column j is
+// btop_of(j), a function of j alone. On: the top starts at block 0, never
+// moves up, and before each column slides down one block when the band's
+// lowest row scores below its upper boundary row, or when it must to reach
+// the last block by column m (docs/DESIGN.md, "Adaptive band";
+// tools/sim_myers.py is the specification). The top is then a per-column
+// fact the traceback has to read back, so the score buffer's column stride
+// grows from K to K + 1 words and word K holds the column's band top.
+template <int K, bool kEmitPath, bool kAdaptive>
 __launch_bounds__(kLanes)
 __global__ void myers_kernel(AlnDeviceArena a, uint32_t num_align) {
+  constexpr int kSStride = kAdaptive ? K + 1 : K;  // sbuf words per column
   const uint32_t wave = blockIdx.x;
   const int lane = threadIdx.x;
   // lanes_per_wave < 64 under-fills waves on purpose: small jobs otherwise
@@ -116,7 +127,10 @@ __global__ void myers_kernel(AlnDeviceArena a, uint32_t num_align) {
       const uint64_t o = (static_cast<uint64_t>(0) * K + b) * 2;
       tb[(o + 0) * kLanes + lane] = Pv[b];
       tb[(o + 1) * kLanes + lane] = Mv[b];
-      sb[(static_cast<uint64_t>(0) * K + b) * kLanes + lane] = S[b];
+      sb[(static_cast<uint64_t>(0) * kSStride + b) * kLanes + lane] = S[b];
+    }
+    if constexpr (kAdaptive) {
+      sb[(static_cast<uint64_t>(0) * kSStride + K) * kLanes + lane] = 0;
     }
   }
 
@@ -124,47 +138,97 @@ __global__ void myers_kernel(AlnDeviceArena a, uint32_t num_align) {
   // Eq words for the next column are prefetched during the current column's
   // recurrence: the gather (64 lanes x scattered 8 B) is the only global
   // read in the loop and would otherwise sit on the critical path.
-  uint64_t EqN[K];
+  //
+  // The adaptive band's top for the next column is only known once this
+  // column is done, so its prefetch takes K + 1 words, blocks btop .. btop + K
+  // of the top it knows, and the column picks its K after the slide decision.
+  // Block btop + K is read only while the band can still slide (btop < hi),
+  // which keeps it below nbt and so inside the wave's peq region.
+  uint64_t EqN[kSStride];
   int32_t btopN = 0;
+  const int32_t hi = nbt > K ? nbt - K : 0;  // adaptive: lowest band top
   if (m > 0) {
     const uint32_t c1 = base_code(t[0]);
-    btopN = btop_of<K>(1, step, nbt);
+    if constexpr (!kAdaptive) {
+      btopN = btop_of<K>(1, step, nbt);
+    }
 #pragma unroll
     for (int b = 0; b < K; ++b) {
       EqN[b] =
           (c1 < 4) ? peq[(static_cast<uint64_t>(btopN + b) * 4 + c1) * kLanes + lane] : 0ull;
     }
+    if constexpr (kAdaptive) {
+      EqN[K] = (c1 < 4 && 0 < hi) ? peq[(static_cast<uint64_t>(K) * 4 + c1) * kLanes + lane]
+                                  : 0ull;
+    }
   }
   for (int32_t j = 1; j <= static_cast<int32_t>(wd.mmax); ++j) {
     if (j <= m) {
       uint64_t EqC[K];
-#pragma unroll
-      for (int b = 0; b < K; ++b) {
-        EqC[b] = EqN[b];
-      }
-      const int32_t btop_new = btopN;
-      if (j < m) {  // issue next column's gather before the compute chain
-        const uint32_t cn = base_code(t[j]);
-        btopN = btop_of<K>(j + 1, step, nbt);
+      if constexpr (!kAdaptive) {
 #pragma unroll
         for (int b = 0; b < K; ++b) {
-          EqN[b] = (cn < 4)
-                       ? peq[(static_cast<uint64_t>(btopN + b) * 4 + cn) * kLanes + lane]
+          EqC[b] = EqN[b];
+        }
+        const int32_t btop_new = btopN;
+        if (j < m) {  // issue next column's gather before the compute chain
+          const uint32_t cn = base_code(t[j]);
+          btopN = btop_of<K>(j + 1, step, nbt);
+#pragma unroll
+          for (int b = 0; b < K; ++b) {
+            EqN[b] = (cn < 4)
+                         ? peq[(static_cast<uint64_t>(btopN + b) * 4 + cn) * kLanes + lane]
+                         : 0ull;
+          }
+        }
+        while (btop < btop_new) {
+          // band slides down one block: drop top, append pessimistic bottom
+#pragma unroll
+          for (int b = 0; b < K - 1; ++b) {
+            Pv[b] = Pv[b + 1];
+            Mv[b] = Mv[b + 1];
+            S[b] = S[b + 1];
+          }
+          Pv[K - 1] = ~0ull;
+          Mv[K - 1] = 0ull;
+          S[K - 1] = S[K - 2] + 64;
+          ++btop;
+        }
+      } else {
+        // scores of column j - 1 on the band's upper boundary row and on its
+        // lowest row; the second condition forces the slides that are left
+        // when only as many columns remain
+        const int32_t top = S[0] - (__popcll(Pv[0]) - __popcll(Mv[0]));
+        const bool slide = btop < hi && (S[K - 1] < top || btop < hi - (m - j));
+#pragma unroll
+        for (int b = 0; b < K; ++b) {
+          EqC[b] = slide ? EqN[b + 1] : EqN[b];
+        }
+        btop += slide ? 1 : 0;
+        if (j < m) {  // issue next column's gather before the compute chain
+          const uint32_t cn = base_code(t[j]);
+#pragma unroll
+          for (int b = 0; b < K; ++b) {
+            EqN[b] = (cn < 4)
+                         ? peq[(static_cast<uint64_t>(btop + b) * 4 + cn) * kLanes + lane]
+                         : 0ull;
+          }
+          EqN[K] = (cn < 4 && btop < hi)
+                       ? peq[(static_cast<uint64_t>(btop + K) * 4 + cn) * kLanes + lane]
                        : 0ull;
         }
-      }
-      while (btop < btop_new) {
-        // band slides down one block: drop top, append pessimistic bottom
+        if (slide) {
+          // drop top, append pessimistic bottom (as above, at most once)
 #pragma unroll
-        for (int b = 0; b < K - 1; ++b) {
-          Pv[b] = Pv[b + 1];
-          Mv[b] = Mv[b + 1];
-          S[b] = S[b + 1];
+          for (int b = 0; b < K - 1; ++b) {
+            Pv[b] = Pv[b + 1];
+            Mv[b] = Mv[b + 1];
+            S[b] = S[b + 1];
+          }
+          Pv[K - 1] = ~0ull;
+          Mv[K - 1] = 0ull;
+          S[K - 1] = S[K - 2] + 64;
         }
-        Pv[K - 1] = ~0ull;
-        Mv[K - 1] = 0ull;
-        S[K - 1] = S[K - 2] + 64;
-        ++btop;
       }
 
       int32_t hin = 1;  // top boundary: D(top-1, j) - D(top-1, j-1) = +1
@@ -193,7 +257,10 @@ __global__ void myers_kernel(AlnDeviceArena a, uint32_t num_align) {
         const uint64_t o = (static_cast<uint64_t>(j) * K + b) * 2;
         tb[(o + 0) * kLanes + lane] = Pv[b];
         tb[(o + 1) * kLanes + lane] = Mv[b];
-        sb[(static_cast<uint64_t>(j) * K + b) * kLanes + lane] = S[b];
+        sb[(static_cast<uint64_t>(j) * kSStride + b) * kLanes + lane] = S[b];
+      }
+      if constexpr (kAdaptive) {
+        sb[(static_cast<uint64_t>(j) * kSStride + K) * kLanes + lane] = btop;
       }
     }
   }
@@ -240,11 +307,25 @@ __global__ void myers_kernel(AlnDeviceArena a, uint32_t num_align) {
     rec = {kAlnBpNone, kAlnBpNone, kAlnBpNone, kAlnBpNone};
   };
   int32_t i = n, j = m;
+  // adaptive: recorded band tops of columns j and j - 1, carried in registers
+  // and shifted when the walk changes column. After a failed final check
+  // (e.g. m < hi: a slide on every column and still short of the last block)
+  // nothing is read: the loop below does not run.
+  auto top_of = [&](int32_t col) {
+    return sb[(static_cast<uint64_t>(col) * kSStride + K) * kLanes + lane];
+  };
+  int32_t rtj = 0, rtj1 = 0;
+  if constexpr (kAdaptive) {
+    if (st == kAlnOk && j > 0) {
+      rtj = top_of(j);
+      rtj1 = top_of(j - 1);
+    }
+  }
   while (st == kAlnOk && i > 0 && j > 0) {
     const int32_t babs = (i - 1) >> 6;
     const uint32_t k = (i - 1) & 63;
-    const int32_t btj = btop_of<K>(j, step, nbt);
-    const int32_t btj1 = btop_of<K>(j - 1, step, nbt);
+    const int32_t btj = kAdaptive ? rtj : btop_of<K>(j, step, nbt);
+    const int32_t btj1 = kAdaptive ? rtj1 : btop_of<K>(j - 1, step, nbt);
     const int32_t rbj = babs - btj;
     const int32_t rbj1 = babs - btj1;
     if (rbj < 0 || rbj >= K || rbj1 < 0 || rbj1 >= K) {
@@ -257,7 +338,12 @@ __global__ void myers_kernel(AlnDeviceArena a, uint32_t num_align) {
     const uint64_t Mvj = tb[(oj + 1) * kLanes + lane];
     const uint64_t Pvj1 = tb[(oj1 + 0) * kLanes + lane];
     const uint64_t Mvj1 = tb[(oj1 + 1) * kLanes + lane];
-    const int32_t S1 = sb[(static_cast<uint64_t>(j - 1) * K + rbj1) * kLanes + lane];
+    const int32_t S1 = sb[(static_cast<uint64_t>(j - 1) * kSStride + rbj1) * kLanes + lane];
+    // adaptive: the top of column j - 2, wanted if this step leaves column j
+    int32_t rtj2 = 0;
+    if constexpr (kAdaptive) {
+      rtj2 = j >= 2 ? top_of(j - 2) : 0;
+    }
 
     const int32_t vd = ((Pvj >> k) & 1) ? 1 : (((Mvj >> k) & 1) ? -1 : 0);
     const int32_t D_left = score_at(S1, Pvj1, Mvj1, k);
@@ -290,6 +376,10 @@ __global__ void myers_kernel(AlnDeviceArena a, uint32_t num_align) {
       --i;
       --j;
       D = D_diag;
+      if constexpr (kAdaptive) {
+        rtj = rtj1;
+        rtj1 = rtj2;
+      }
     } else if (D_left + 1 == D) {
       if constexpr (kEmitPath) {
         path[plen++] = 2;  // D (consume target)
@@ -301,6 +391,10 @@ __global__ void myers_kernel(AlnDeviceArena a, uint32_t num_align) {
       }
       --j;
       D = D_left;
+      if constexpr (kAdaptive) {
+        rtj = rtj1;
+        rtj1 = rtj2;
+      }
     } else if ((D - vd) + 1 == D) {
       if constexpr (kEmitPath) {
         path[plen++] = 1;  // I (consume query)
@@ -341,32 +435,42 @@ __global__ void myers_kernel(AlnDeviceArena a, uint32_t num_align) {
 }  // namespace
 
 namespace {
-template <int K>
+template <int K, bool kAdaptive>
 void launch_k(const AlnDeviceArena& arena, uint32_t num_waves, uint32_t num_align,
               bool emit_path, hipStream_t s) {
   if (emit_path) {
-    hipLaunchKernelGGL((myers_kernel<K, true>), dim3(num_waves), dim3(kLanes), 0, s, arena,
-                       num_align);
+    hipLaunchKernelGGL((myers_kernel<K, true, kAdaptive>), dim3(num_waves), dim3(kLanes), 0, s,
+                       arena, num_align);
   } else {
-    hipLaunchKernelGGL((myers_kernel<K, false>), dim3(num_waves), dim3(kLanes), 0, s, arena,
-                       num_align);
+    hipLaunchKernelGGL((myers_kernel<K, false, kAdaptive>), dim3(num_waves), dim3(kLanes), 0, s,
+                       arena, num_align);
+  }
+}
+
+template <bool kAdaptive>
+void launch_policy(const AlnDeviceArena& arena, uint32_t num_waves, uint32_t num_align,
+                   uint32_t band_k, bool emit_path, hipStream_t s) {
+  switch (band_k) {
+    case 4:
+      launch_k<4, kAdaptive>(arena, num_waves, num_align, emit_path, s);
+      break;
+    case 8:
+      launch_k<8, kAdaptive>(arena, num_waves, num_align, emit_path, s);
+      break;
+    default:
+      launch_k<16, kAdaptive>(arena, num_waves, num_align, emit_path, s);
+      break;
   }
 }
 }  // namespace
 
 void launch_aligner_kernel(const AlnDeviceArena& arena, uint32_t num_waves, uint32_t num_align,
-                           uint32_t band_k, bool emit_path, void* stream) {
+                           uint32_t band_k, bool emit_path, bool adaptive, void* stream) {
   auto s = static_cast<hipStream_t>(stream);
-  switch (band_k) {
-    case 4:
-      launch_k<4>(arena, num_waves, num_align, emit_path, s);
-      break;
-    case 8:
-      launch_k<8>(arena, num_waves, num_align, emit_path, s);
-      break;
-    default:
-      launch_k<16>(arena, num_waves, num_align, emit_path, s);
-      break;
+  if (adaptive) {
+    launch_policy<true>(arena, num_waves, num_align, band_k, emit_path, s);
+  } else {
+    launch_policy<false>(arena, num_waves, num_align, band_k, emit_path, s);
   }
 }
 

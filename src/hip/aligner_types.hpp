@@ -56,7 +56,8 @@ constexpr uint32_t kAlnBpNone = 0xffffffffu;
 struct AlnWaveDesc {
   uint64_t peq_off;  // u64 units: [(block*4 + code)*64 + lane]
   uint64_t tb_off;   // u64 units: [((col*K + block)*2 + {Pv,Mv})*64 + lane]
-  uint64_t s_off;    // i32 units: [(col*K + block)*64 + lane]
+  uint64_t s_off;    // i32 units: [(col*K + block)*64 + lane]; the adaptive
+                     // kernel's columns are K+1 words, word K = band top
   uint32_t nb;       // query blocks allocated in peq for this wave (>= K)
   uint32_t mmax;     // max t_len in this wave (uniform column loop bound)
 };
@@ -81,12 +82,25 @@ struct AlnDeviceArena {
   AlnLimits limits;
 };
 
+// Where the band of K blocks lies. kDiagonal: on the rectangle diagonal.
+// kAdaptive: it starts at block 0 and follows the scores downwards. kRetry:
+// diagonal first, then adaptive at the same K over the alignments that came
+// back kAlnBandEdge (the two policies cover different ground).
+enum class AlnBandPolicy : int32_t { kDiagonal = 0, kAdaptive = 1, kRetry = 2 };
+
+// sbuf words per column: the adaptive kernel records the column's band top
+// after the K block-bottom scores.
+constexpr uint32_t aln_s_stride(uint32_t band_k, bool adaptive) {
+  return adaptive ? band_k + 1 : band_k;
+}
+
 // Launches the K-block Myers kernel over `num_align` sorted alignments
 // packed arena.lanes_per_wave to a wave. band_k must be 4, 8 or 16. With
 // emit_path the traceback writes path / path_len; without it the traceback
 // writes the window records (arena.bp, arena.window_length) and leaves the
-// path arena alone.
+// path arena alone. `adaptive` selects the adaptive-band kernel, whose waves'
+// sbuf regions hold aln_s_stride(band_k, true) words per column.
 void launch_aligner_kernel(const AlnDeviceArena& arena, uint32_t num_waves, uint32_t num_align,
-                           uint32_t band_k, bool emit_path, void* stream);
+                           uint32_t band_k, bool emit_path, bool adaptive, void* stream);
 
 }  // namespace rga::hip

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Dev-time simulator of the banded blocked-Myers kernel in
 src/hip/aligner_kernel.hip — validates the recurrence, band slide, score
-reconstruction and traceback logic against brute-force DP on random pairs.
+reconstruction and traceback logic against brute-force DP on random pairs,
+for both band policies: the diagonal band (btop_of) and the adaptive band
+that follows the scores (docs/DESIGN.md, "Adaptive band").
 Run: python tools/sim_myers.py [K] [trials]
 """
 
@@ -39,9 +41,19 @@ def score_at(S, Pv, Mv, k):
     return S - (bin(Pv & mask).count("1") - bin(Mv & mask).count("1"))
 
 
-def align(q, t, K):
+def popcount(x):
+    return bin(x).count("1")
+
+
+def align(q, t, K, adaptive=False):
+    """Returns (edit_distance, path, status). With adaptive the band top
+    starts at block 0, never moves up, and before each column slides down one
+    block when the band's lowest row scores below its upper boundary row (or
+    when it must, to reach the last block by column m); the tops are recorded
+    per column for the traceback."""
     n, m = len(q), len(t)
     nbt = (n + 63) >> 6
+    hi = nbt - K if nbt > K else 0
     # peq
     nb = max(K, nbt)
     peq = [[0] * 4 for _ in range(nb)]
@@ -54,13 +66,21 @@ def align(q, t, K):
     Mv = [0] * K
     S = [(b + 1) * 64 for b in range(K)]
     btop = 0
+    tops = [0] * (m + 1)  # band top per column (adaptive: as it moved)
     tb = {}  # (j, rb) -> (Pv, Mv, S)
     for b in range(K):
         tb[(0, b)] = (Pv[b], Mv[b], S[b])
 
     for j in range(1, m + 1):
         c = base_code(t[j - 1])
-        btn = btop_of(j, n, m, nbt, K)
+        if adaptive:
+            top = S[0] - (popcount(Pv[0]) - popcount(Mv[0]))
+            bot = S[K - 1]
+            slide = btop < hi and (bot < top or btop < hi - (m - j))
+            btn = btop + 1 if slide else btop
+        else:
+            btn = btop_of(j, n, m, nbt, K)
+        tops[j] = btn
         while btop < btn:
             for b in range(K - 1):
                 Pv[b], Mv[b], S[b] = Pv[b + 1], Mv[b + 1], S[b + 1]
@@ -97,8 +117,11 @@ def align(q, t, K):
     while i > 0 and j > 0:
         babs = (i - 1) >> 6
         k = (i - 1) & 63
-        btj = btop_of(j, n, m, nbt, K)
-        btj1 = btop_of(j - 1, n, m, nbt, K)
+        if adaptive:
+            btj, btj1 = tops[j], tops[j - 1]
+        else:
+            btj = btop_of(j, n, m, nbt, K)
+            btj1 = btop_of(j - 1, n, m, nbt, K)
         rbj = babs - btj
         rbj1 = babs - btj1
         if not (0 <= rbj < K and 0 <= rbj1 < K):
@@ -166,7 +189,7 @@ def main():
     K = int(sys.argv[1]) if len(sys.argv) > 1 else 4
     trials = int(sys.argv[2]) if len(sys.argv) > 2 else 60
     rng = random.Random(1)
-    fails = edges = 0
+    fails = edges = a_edges = a_exact = 0
     for trial in range(trials):
         m = rng.randint(3, 700)
         t = "".join(rng.choice("ACGT") for _ in range(m))
@@ -180,16 +203,30 @@ def main():
         ed, path, st = align(q, t, K)
         if st != "ok":
             edges += 1
-            continue
-        if ed != ref:
+        elif ed != ref and (ed < ref or ref <= 64 * K // 2 - 64):
             # band may truncate the optimum for wildly divergent pairs:
             # only equal-or-worse is acceptable, and only when divergent
-            if ed < ref or ref <= 64 * K // 2 - 64:
-                print(f"FAIL trial {trial}: ed={ed} ref={ref} n={len(q)} m={m}")
-                fails += 1
-                continue
-        check_path(q, t, path, ed)
-    print(f"K={K}: {trials} trials, {fails} fails, {edges} band-edge")
+            print(f"FAIL trial {trial}: ed={ed} ref={ref} n={len(q)} m={m}")
+            fails += 1
+        else:
+            check_path(q, t, path, ed)
+        # adaptive band: never below the optimum, a status-ok path always
+        # replays to the reported distance, and a query that fits the band
+        # (the band cannot move) gives exactly the diagonal result
+        aed, apath, ast = align(q, t, K, adaptive=True)
+        if len(q) <= 64 * K and (aed, apath, ast) != (ed, path, st):
+            print(f"FAIL trial {trial}: adaptive differs at n={len(q)} <= {64 * K}")
+            fails += 1
+        if ast != "ok":
+            a_edges += 1
+        elif aed < ref:
+            print(f"FAIL trial {trial}: adaptive ed={aed} below ref={ref}")
+            fails += 1
+        else:
+            check_path(q, t, apath, aed)
+            a_exact += aed == ref
+    print(f"K={K}: {trials} trials, {fails} fails, {edges} band-edge (diagonal), "
+          f"{a_edges} band-edge / {a_exact} optimal (adaptive)")
     return 1 if fails else 0
 
 
