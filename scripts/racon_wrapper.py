@@ -8,7 +8,7 @@ with concatenated stdout. Two deliberate improvements over the reference:
 
 * GPU flags (-c/--cudapoa-batches, --cudaaligner-batches,
   -b/--cuda-banded-alignment, --cudaaligner-band-width,
-  --aligner-adaptive-band) are ACTUALLY
+  --aligner-adaptive-band, --aligner-wide-band) are ACTUALLY
   forwarded to racon; the reference parses but drops them
   (racon_wrapper.py:38-40,130-131 are commented out there).
 * binaries are located at runtime (RACON_BIN / RAMPLER_BIN env vars, then
@@ -82,6 +82,9 @@ def main():
     parser.add_argument("--aligner-adaptive-band", action="store_true",
                         help="second GPU pass, with an adaptive band, over overlaps "
                              "that escape the alignment band")
+    parser.add_argument("--aligner-wide-band", action="store_true",
+                        help="last GPU pass, one wavefront per overlap with a band of "
+                             "4096, over overlaps that are still escaped")
     parser.add_argument("--in-process", action="store_true",
                         help="polish every --split chunk inside ONE process via the "
                              "_racon module instead of one racon subprocess per chunk: "
@@ -148,7 +151,8 @@ def main():
                     aligner_batches=int(args.cudaaligner_batches),
                     aligner_band_width=int(args.cudaaligner_band_width),
                     include_unpolished=args.include_unpolished,
-                    aligner_adaptive_band=args.aligner_adaptive_band)
+                    aligner_adaptive_band=args.aligner_adaptive_band,
+                    aligner_wide_band=args.aligner_wide_band)
                 for name, seq in out:
                     sys.stdout.write(f">{name}\n{seq}\n")
                 sys.stdout.flush()
@@ -174,6 +178,8 @@ def main():
             cmd += ["--cudaaligner-band-width", str(args.cudaaligner_band_width)]
         if args.aligner_adaptive_band:
             cmd.append("--aligner-adaptive-band")
+        if args.aligner_wide_band:
+            cmd.append("--aligner-wide-band")
         cmd += [sequences, overlaps, None]
 
         for chunk in chunks:

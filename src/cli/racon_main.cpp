@@ -17,6 +17,7 @@ namespace {
 constexpr int32_t kAlignerBatchesOpt = 10000;
 constexpr int32_t kAlignerBandWidthOpt = 10001;
 constexpr int32_t kAlignerAdaptiveBandOpt = 10002;
+constexpr int32_t kAlignerWideBandOpt = 10003;
 
 struct option long_options[] = {
     {"include-unpolished", no_argument, nullptr, 'u'},
@@ -36,6 +37,7 @@ struct option long_options[] = {
     {"cudaaligner-batches", required_argument, nullptr, kAlignerBatchesOpt},
     {"cudaaligner-band-width", required_argument, nullptr, kAlignerBandWidthOpt},
     {"aligner-adaptive-band", no_argument, nullptr, kAlignerAdaptiveBandOpt},
+    {"aligner-wide-band", no_argument, nullptr, kAlignerWideBandOpt},
     {nullptr, 0, nullptr, 0}};
 
 void help() {
@@ -101,7 +103,12 @@ void help() {
       "        --aligner-adaptive-band\n"
       "            give overlaps that escape the alignment band a second pass on the\n"
       "            GPU, with a band that follows the scores, before the CPU aligner\n"
-      "            takes them (no effect without --cudaaligner-batches)\n");
+      "            takes them (no effect without --cudaaligner-batches)\n"
+      "        --aligner-wide-band\n"
+      "            give overlaps that are still escaped a last pass on the GPU, one\n"
+      "            wavefront per overlap with a band of 4096, before the CPU aligner\n"
+      "            takes them (independent of --aligner-adaptive-band; no effect\n"
+      "            without --cudaaligner-batches)\n");
 }
 
 }  // namespace
@@ -140,6 +147,7 @@ int main(int argc, char** argv) {
       case kAlignerBatchesOpt: config.aligner_batches = atoi(optarg); break;
       case kAlignerBandWidthOpt: config.aligner_band_width = atoi(optarg); break;
       case kAlignerAdaptiveBandOpt: config.aligner_adaptive_band = true; break;
+      case kAlignerWideBandOpt: config.aligner_wide_band = true; break;
       default: exit(1);
     }
   }

@@ -49,6 +49,10 @@ struct PolisherConfig {
   // pass at the same width before the CPU aligner takes them (HIP aligner
   // batches only)
   bool aligner_adaptive_band = false;
+  // last GPU pass for overlaps that are still escaped after that: one
+  // wavefront per overlap with a band of 4096 (hip::AlnBandPolicy::kWide's
+  // kernel). Off by default; independent of aligner_adaptive_band.
+  bool aligner_wide_band = false;
 };
 
 class Polisher {

@@ -162,6 +162,7 @@ void AlignerBatch::allocate_arenas(size_t mem_budget) {
   d_waves_ = reinterpret_cast<AlnWaveDesc*>(base + o_waves);
   arena_.order = d_order_;
   arena_.waves = d_waves_;
+  max_waves_ = max_waves;
   arena_.lanes_per_wave = kLanes;
   arena_.limits = limits_;
 }
@@ -343,6 +344,42 @@ void AlignerBatch::launch_pass(std::vector<uint32_t> order, bool adaptive,
   }
 }
 
+void AlignerBatch::launch_wide_pass(std::vector<uint32_t> order, std::vector<uint32_t>* never_run,
+                                    std::vector<uint32_t>* refused) {
+  auto s = static_cast<hipStream_t>(stream_);
+  // longest first: a wave lasts as long as its alignment
+  aln_sort_for_launch(h_descs_, &order);
+  const uint32_t count = static_cast<uint32_t>(order.size());
+  std::copy(order.begin(), order.end(), h_order_);
+  RGA_HIP_CHECK(hipMemcpyAsync(d_order_, h_order_, count * 4, hipMemcpyHostToDevice, s));
+  // one descriptor per alignment: the descriptor arrays, sized for the lane
+  // kernel's waves, take the pass in pieces
+  for (uint32_t begin = 0; begin < count; begin += max_waves_) {
+    const uint32_t piece = std::min(max_waves_, count - begin);
+    const AlnWavePlan plan = aln_plan_wave_launches(h_descs_, h_order_ + begin, piece,
+                                                    {peq_cap_u64_, tb_cap_u64_, s_cap_i32_});
+    never_run->insert(never_run->end(), plan.never_run.begin(), plan.never_run.end());
+    refused->insert(refused->end(), plan.refused.begin(), plan.refused.end());
+    if (plan.launches.empty()) {
+      continue;
+    }
+    if (begin > 0) {
+      RGA_HIP_CHECK(hipStreamSynchronize(s));  // the copy of the piece before read h_waves_
+    }
+    std::copy(plan.waves.begin(), plan.waves.end(), h_waves_);
+    RGA_HIP_CHECK(hipMemcpyAsync(d_waves_, h_waves_, plan.waves.size() * sizeof(AlnWaveDesc),
+                                 hipMemcpyHostToDevice, s));
+    for (const AlnSubLaunch& l : plan.launches) {
+      AlnDeviceArena launch_arena = arena_;
+      launch_arena.order = d_order_ + begin + l.first_wave;
+      launch_arena.waves = d_waves_ + l.desc_off;
+      launch_arena.lanes_per_wave = 1;
+      launch_arena.window_length = window_length_;
+      launch_aligner_wave_kernel(launch_arena, l.num_align, window_length_ == 0, stream_);
+    }
+  }
+}
+
 void AlignerBatch::read_back() {
   auto s = static_cast<hipStream_t>(stream_);
   const uint32_t na = static_cast<uint32_t>(overlaps_.size());
@@ -361,6 +398,7 @@ void AlignerBatch::read_back() {
 
 void AlignerBatch::run() {
   retry_completed_ = 0;
+  wide_completed_ = 0;
   if (overlaps_.empty()) {
     return;
   }
@@ -376,6 +414,23 @@ void AlignerBatch::run() {
   std::vector<uint32_t> all(na);
   std::iota(all.begin(), all.end(), 0u);
   std::vector<uint32_t> never_run;  // original indices of un-runnable waves
+  if (policy_ == AlnBandPolicy::kWide) {
+    // the wave kernel alone; what it refuses comes back as an escape
+    std::vector<uint32_t> refused;
+    launch_wide_pass(std::move(all), &never_run, &refused);
+    read_back();
+    for (uint32_t orig : never_run) {
+      h_status_[orig] = kAlnNotRun;
+      h_path_len_[orig] = 0;
+      h_edit_[orig] = -1;
+    }
+    for (uint32_t orig : refused) {
+      h_status_[orig] = kAlnBandEdge;
+      h_path_len_[orig] = 0;
+      h_edit_[orig] = -1;
+    }
+    return;
+  }
   launch_pass(std::move(all), policy_ == AlnBandPolicy::kAdaptive, &never_run);
   read_back();
   // the device never wrote these alignments' results
@@ -387,32 +442,51 @@ void AlignerBatch::run() {
     }
   };
   mark_never_run();
-  if (policy_ != AlnBandPolicy::kRetry) {
-    return;
-  }
-
-  // second chance: the adaptive band at the same K over the escaped
-  // alignments only, on the arena as packed. The kernel writes results of
-  // the alignments it runs and of no other, so the device still holds the
-  // first pass's for the rest and the second read-back returns them as
-  // they were.
-  std::vector<uint32_t> escaped;
-  for (uint32_t i = 0; i < na; ++i) {
-    if (h_status_[i] == kAlnBandEdge) {
-      escaped.push_back(i);
+  // alignments still escaped, for the pass that follows
+  auto escaped_now = [&] {
+    std::vector<uint32_t> escaped;
+    for (uint32_t i = 0; i < na; ++i) {
+      if (h_status_[i] == kAlnBandEdge) {
+        escaped.push_back(i);
+      }
+    }
+    return escaped;
+  };
+  if (policy_ == AlnBandPolicy::kRetry) {
+    // second chance: the adaptive band at the same K over the escaped
+    // alignments only, on the arena as packed. The kernel writes results of
+    // the alignments it runs and of no other, so the device still holds the
+    // first pass's for the rest and the second read-back returns them as
+    // they were.
+    const std::vector<uint32_t> escaped = escaped_now();
+    if (!escaped.empty()) {
+      // a wave the adaptive pass cannot launch leaves its alignments as the
+      // first pass reported them (kAlnBandEdge)
+      std::vector<uint32_t> not_retried;
+      launch_pass(escaped, true, &not_retried);
+      read_back();
+      mark_never_run();
+      for (uint32_t i : escaped) {
+        retry_completed_ += h_status_[i] == kAlnOk ? 1 : 0;
+      }
     }
   }
+  if (!wide_pass_) {
+    return;
+  }
+  // last chance before the CPU: the wave kernel over what is still escaped.
+  // Again the device holds the earlier results of every alignment this pass
+  // does not run, the ones it refuses or cannot hold included.
+  const std::vector<uint32_t> escaped = escaped_now();
   if (escaped.empty()) {
     return;
   }
-  // a wave the adaptive pass cannot launch leaves its alignments as the
-  // first pass reported them (kAlnBandEdge)
-  std::vector<uint32_t> not_retried;
-  launch_pass(escaped, true, &not_retried);
+  std::vector<uint32_t> not_run, refused;
+  launch_wide_pass(escaped, &not_run, &refused);
   read_back();
   mark_never_run();
   for (uint32_t i : escaped) {
-    retry_completed_ += h_status_[i] == kAlnOk ? 1 : 0;
+    wide_completed_ += h_status_[i] == kAlnOk ? 1 : 0;
   }
 }
 
@@ -465,9 +539,13 @@ std::vector<std::pair<uint32_t, uint32_t>> AlignerBatch::breaking_points_of(
   return points;
 }
 
-uint32_t AlignerBatch::align_and_emit(uint32_t window_length, uint32_t* adaptive_completed) {
+uint32_t AlignerBatch::align_and_emit(uint32_t window_length, uint32_t* adaptive_completed,
+                                      uint32_t* wide_completed) {
   if (adaptive_completed != nullptr) {
     *adaptive_completed = 0;
+  }
+  if (wide_completed != nullptr) {
+    *wide_completed = 0;
   }
   if (overlaps_.empty()) {
     return 0;
@@ -475,6 +553,9 @@ uint32_t AlignerBatch::align_and_emit(uint32_t window_length, uint32_t* adaptive
   run();
   if (adaptive_completed != nullptr) {
     *adaptive_completed = retry_completed_;
+  }
+  if (wide_completed != nullptr) {
+    *wide_completed = wide_completed_;
   }
   if (window_length_ > 0) {
     // breaking-point mode: a few records per overlap, nothing worth threads.

@@ -59,14 +59,26 @@ class AlignerBatch {
   void set_band_policy(AlnBandPolicy policy) { policy_ = policy; }
   AlnBandPolicy band_policy() const { return policy_; }
 
+  // Last pass before the CPU aligner (off unless set): the alignments that
+  // the policy's own passes leave kAlnBandEdge go through the wave kernel,
+  // one wavefront per alignment with a band of 4096. Like the policy, a
+  // property of the use: whoever takes a pooled batch sets it.
+  void set_wide_pass(bool on) { wide_pass_ = on; }
+  bool wide_pass() const { return wide_pass_; }
+
   // Runs the kernel over everything reserved (pack + sub-launches + D2H). In
   // breaking-point mode the records come back instead of path / path_len.
   // Under kRetry a second, adaptive pass runs over the alignments the
   // diagonal pass returned as kAlnBandEdge; every other alignment keeps its
-  // first-pass result, and kAlnNotRun alignments are not retried.
+  // first-pass result, and kAlnNotRun alignments are not retried. The wide
+  // pass, when set, follows under the same rules. Under kWide the wave kernel
+  // is the only pass; a pair it refuses (aln_wave_single_slide) comes back
+  // kAlnBandEdge.
   void run();
   // Alignments the last run()'s second pass completed (kRetry only).
   uint32_t retry_completed() const { return retry_completed_; }
+  // Alignments the last run()'s wide pass completed (set_wide_pass only).
+  uint32_t wide_completed() const { return wide_completed_; }
   // Post-run accessors per slot.
   int32_t status_of(uint32_t slot) const { return h_status_[slot]; }
   int32_t edit_distance_of(uint32_t slot) const { return h_edit_[slot]; }
@@ -91,8 +103,10 @@ class AlignerBatch {
   // batches' kernels instead of serializing in the post-GPU CPU pass.
   // Returns how many overlaps fell back (band-edge -> CPU aligner); under
   // kRetry that is the count after the second pass, and *adaptive_completed
-  // (when given) gets the number of overlaps the second pass completed.
-  uint32_t align_and_emit(uint32_t window_length = 0, uint32_t* adaptive_completed = nullptr);
+  // (when given) gets the number of overlaps the second pass completed, and
+  // *wide_completed the number the wide pass completed.
+  uint32_t align_and_emit(uint32_t window_length = 0, uint32_t* adaptive_completed = nullptr,
+                          uint32_t* wide_completed = nullptr);
 
   void reset();
 
@@ -103,6 +117,12 @@ class AlignerBatch {
   // plans the sub-launches and enqueues them. Alignments of waves that can
   // never launch are appended to *never_run.
   void launch_pass(std::vector<uint32_t> order, bool adaptive, std::vector<uint32_t>* never_run);
+  // One pass of the wave kernel over the alignments in `order`. Alignments
+  // whose state no arena can hold are appended to *never_run, those the
+  // kernel's schedule does not cover to *refused; neither is touched on the
+  // device.
+  void launch_wide_pass(std::vector<uint32_t> order, std::vector<uint32_t>* never_run,
+                        std::vector<uint32_t>* refused);
   // D2H of the products and statuses, then a stream sync.
   void read_back();
 
@@ -117,6 +137,7 @@ class AlignerBatch {
   uint64_t tb_cap_u64_, s_cap_i32_, peq_cap_u64_;
   uint64_t fill_cap_u64_;  // tb words one fill may reserve
   uint32_t max_alignments_;
+  uint32_t max_waves_ = 0;  // descriptors h_waves_ / d_waves_ hold
 
   uint8_t* h_seqs_ = nullptr;
   AlnDesc* h_descs_ = nullptr;
@@ -139,7 +160,9 @@ class AlignerBatch {
   size_t bp_records_ = 0;     // window records reserved
   uint32_t window_length_ = 0;  // of the current fill; 0 = path mode
   AlnBandPolicy policy_ = AlnBandPolicy::kDiagonal;
+  bool wide_pass_ = false;
   uint32_t retry_completed_ = 0;
+  uint32_t wide_completed_ = 0;
   std::vector<Overlap*> overlaps_;
   struct PendingSpan {
     const char* q;

@@ -112,4 +112,71 @@ AlnLaunchPlan aln_plan_launches(const AlnDesc* descs, const uint32_t* order, uin
   return plan;
 }
 
+bool aln_wave_single_slide(uint32_t q_len, uint32_t t_len) {
+  if (t_len == 0) {
+    return false;
+  }
+  if (q_len <= 64ull * t_len) {
+    return true;  // the band centre moves at most 64 rows per column
+  }
+  // t_len < q_len / 64 here, a few thousand columns at most: walk the rule
+  // (btop_of of the kernels at K = 64)
+  const uint64_t step = (static_cast<uint64_t>(q_len) << 32) / t_len;
+  const int64_t nbt = (q_len + 63) / 64;
+  const int64_t hi = nbt > kAlnWaveBandK ? nbt - kAlnWaveBandK : 0;
+  int64_t prev = 0;
+  for (uint64_t j = 1; j <= t_len; ++j) {
+    const int64_t center_blk = static_cast<int64_t>(static_cast<uint32_t>((j * step) >> 32) >> 6);
+    const int64_t top = std::max<int64_t>(0, std::min(center_blk - kAlnWaveBandK / 2, hi));
+    if (top - prev > 1) {
+      return false;
+    }
+    prev = top;
+  }
+  return true;
+}
+
+AlnWavePlan aln_plan_wave_launches(const AlnDesc* descs, const uint32_t* order, uint32_t count,
+                                   const AlnArenaCaps& caps) {
+  AlnWavePlan plan;
+  AlnSubLaunch launch{0, 0, 0, 0};
+  uint64_t tb_off = 0, s_off = 0;
+  auto close_launch = [&] {
+    if (launch.num_waves > 0) {
+      launch.num_align = launch.num_waves;
+      plan.launches.push_back(launch);
+    }
+    launch.num_waves = 0;
+    tb_off = s_off = 0;
+  };
+  for (uint32_t w = 0; w < count; ++w) {
+    const AlnDesc& d = descs[order[w]];
+    const uint64_t steps = aln_wave_steps(d.q_len, d.t_len);
+    const uint64_t tb = steps * kAlnWaveTbPerStep, s = steps * kAlnWaveSPerStep;
+    const bool fits = tb <= caps.tb_u64 && s <= caps.s_i32;
+    if (!fits || !aln_wave_single_slide(d.q_len, d.t_len)) {
+      // no descriptor: the launch before it ends here
+      close_launch();
+      (fits ? plan.refused : plan.never_run).push_back(order[w]);
+      continue;
+    }
+    if (tb_off + tb > caps.tb_u64 || s_off + s > caps.s_i32) {
+      close_launch();
+    }
+    if (launch.num_waves == 0) {
+      launch.first_wave = w;
+      launch.desc_off = static_cast<uint32_t>(plan.waves.size());
+    }
+    AlnWaveDesc wd{};  // the wave kernel reads the two offsets and nothing else
+    wd.tb_off = tb_off;
+    wd.s_off = s_off;
+    plan.waves.push_back(wd);
+    tb_off += tb;
+    s_off += s;
+    ++launch.num_waves;
+  }
+  close_launch();
+  return plan;
+}
+
 }  // namespace rga::hip

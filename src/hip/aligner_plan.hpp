@@ -6,7 +6,9 @@
 // length and cuts the waves into sub-launches, each of which fits the
 // per-column state arenas (peq / tb / sbuf) at once. AlignerBatch plans its
 // diagonal pass and, under the retry policy, the adaptive pass over the
-// escaped alignments with the same code.
+// escaped alignments with the same code. The wide pass (one wavefront per
+// alignment, state indexed by step) has a planner of its own at the end of
+// this file, checked the same way (tests/aligner_wide_plan_check.cpp).
 #pragma once
 
 #include <cstdint>
@@ -52,5 +54,30 @@ void aln_sort_for_launch(const AlnDesc* descs, std::vector<uint32_t>* order);
 AlnLaunchPlan aln_plan_launches(const AlnDesc* descs, const uint32_t* order, uint32_t count,
                                 uint32_t lanes, uint32_t band_k, uint32_t s_stride,
                                 const AlnArenaCaps& caps);
+
+// ---- wide pass: one wavefront per alignment (aligner_wave_kernel.hip) ----
+
+// True when the diagonal band at K = 64 slides at most one block per column
+// for a q_len x t_len rectangle. The wave kernel's schedule needs that; the
+// other pairs (q_len > 64 * t_len and more than 64 query blocks) are refused.
+bool aln_wave_single_slide(uint32_t q_len, uint32_t t_len);
+
+// `launches` cut `order` as AlnSubLaunch describes with one alignment per
+// wave: first_wave is the position in `order` and every launched alignment
+// has one descriptor. Alignments in never_run or refused have none and lie
+// between launches.
+struct AlnWavePlan {
+  std::vector<AlnWaveDesc> waves;
+  std::vector<AlnSubLaunch> launches;
+  std::vector<uint32_t> never_run;  // state alone exceeds the tb or sbuf arena
+  std::vector<uint32_t> refused;    // not aln_wave_single_slide
+};
+
+// Cuts the pass over order[0 .. count) into sub-launches whose step-indexed
+// states (aln_wave_steps x kAlnWaveTbPerStep / kAlnWaveSPerStep) fit the tb
+// and sbuf arenas together. caps.peq_u64 is not used: the kernel builds its
+// masks in registers.
+AlnWavePlan aln_plan_wave_launches(const AlnDesc* descs, const uint32_t* order, uint32_t count,
+                                   const AlnArenaCaps& caps);
 
 }  // namespace rga::hip

@@ -86,7 +86,9 @@ struct AlnDeviceArena {
 // kAdaptive: it starts at block 0 and follows the scores downwards. kRetry:
 // diagonal first, then adaptive at the same K over the alignments that came
 // back kAlnBandEdge (the two policies cover different ground).
-enum class AlnBandPolicy : int32_t { kDiagonal = 0, kAdaptive = 1, kRetry = 2 };
+// kWide: every alignment goes through the wave kernel below (one wavefront per
+// alignment, band 4096), whatever the batch's own band.
+enum class AlnBandPolicy : int32_t { kDiagonal = 0, kAdaptive = 1, kRetry = 2, kWide = 3 };
 
 // sbuf words per column: the adaptive kernel records the column's band top
 // after the K block-bottom scores.
@@ -102,5 +104,27 @@ constexpr uint32_t aln_s_stride(uint32_t band_k, bool adaptive) {
 // sbuf regions hold aln_s_stride(band_k, true) words per column.
 void launch_aligner_kernel(const AlnDeviceArena& arena, uint32_t num_waves, uint32_t num_align,
                            uint32_t band_k, bool emit_path, bool adaptive, void* stream);
+
+// ---- wide band: one wavefront per alignment (aligner_wave_kernel.hip) ----
+//
+// The band is kAlnWaveBandK blocks, one per lane. Column states are stored by
+// step, [step][lane], in the same tb / sbuf arenas: per step 64 x 16 B of
+// Pv/Mv and 64 x 4 B of scores. Block B of column j is stored at step j + B,
+// so an alignment needs t_len + 64 + query blocks + 1 steps.
+constexpr uint32_t kAlnWaveBandK = 64;
+constexpr uint32_t kAlnWaveTbPerStep = 2 * 64;  // u64 words of tb per step
+constexpr uint32_t kAlnWaveSPerStep = 64;       // i32 words of sbuf per step
+constexpr uint64_t aln_wave_steps(uint32_t q_len, uint32_t t_len) {
+  return static_cast<uint64_t>(t_len) + 64 + (q_len + 63) / 64 + 1;
+}
+
+// Launches the wave kernel: one 64-lane workgroup per alignment, alignment
+// order[w] with the tb / sbuf offsets of waves[w] (peq_off, nb and mmax are
+// not used). The band lies as the lane kernel's diagonal band would at
+// K = 64 and the products are the same: path / path_len with emit_path, the
+// window records without. Every alignment must satisfy aln_wave_single_slide
+// (aligner_plan.hpp).
+void launch_aligner_wave_kernel(const AlnDeviceArena& arena, uint32_t num_align, bool emit_path,
+                                void* stream);
 
 }  // namespace rga::hip

@@ -196,6 +196,7 @@ class HipPolisher : public Polisher {
     uint64_t next_overlap = 0;
     std::atomic<uint64_t> skipped{0};
     std::atomic<uint64_t> adaptive_completed{0};
+    std::atomic<uint64_t> wide_completed{0};
     std::atomic<int64_t> t_fill_ns{0}, t_gpu_ns{0};
 
     auto worker = [&](hip::AlignerBatch* batch) {
@@ -203,6 +204,7 @@ class HipPolisher : public Polisher {
       // pooled batches carry no policy of their own
       batch->set_band_policy(config_.aligner_adaptive_band ? hip::AlnBandPolicy::kRetry
                                                            : hip::AlnBandPolicy::kDiagonal);
+      batch->set_wide_pass(config_.aligner_wide_band);
       while (true) {
         batch->reset();
         uint32_t pulled = 0;
@@ -233,9 +235,10 @@ class HipPolisher : public Polisher {
         if (pulled == 0) {
           return;
         }
-        uint32_t second_pass = 0;
-        skipped += batch->align_and_emit(config_.window_length, &second_pass);
+        uint32_t second_pass = 0, wide_pass = 0;
+        skipped += batch->align_and_emit(config_.window_length, &second_pass, &wide_pass);
         adaptive_completed += second_pass;
+        wide_completed += wide_pass;
         t_gpu_ns += (clk::now() - t1).count();
       }
     };
@@ -264,6 +267,10 @@ class HipPolisher : public Polisher {
     if (adaptive_completed.load() > 0) {
       fprintf(stderr, "[rga::HipPolisher] %lu overlap(s) completed by the adaptive band\n",
               static_cast<unsigned long>(adaptive_completed.load()));
+    }
+    if (wide_completed.load() > 0) {
+      fprintf(stderr, "[rga::HipPolisher] %lu overlap(s) completed by the wide band\n",
+              static_cast<unsigned long>(wide_completed.load()));
     }
     // CPU pass: walks CIGARs into breaking points; aligns leftovers with the
     // CPU pairwise engine
@@ -564,16 +571,18 @@ poa_window_graph_gpu(const RawWindows& window_layers, int8_t match, int8_t misma
 // Direct GPU alignment of raw (query, target) pairs — numerics testing
 // entry (GPU edit distance must equal the CPU optimum; CIGARs must be
 // consistent). Returns (cigar, edit_distance, status) per pair. `policy` is
-// the band policy of every run (AlnBandPolicy).
+// the band policy of every run (AlnBandPolicy), `wide_pass` whether the wide
+// band follows it (AlignerBatch::set_wide_pass).
 std::vector<std::tuple<std::string, int32_t, int32_t>> align_pairs(
     const std::vector<std::pair<std::string, std::string>>& pairs, uint32_t band_width,
-    AlnBandPolicy policy) {
+    AlnBandPolicy policy, bool wide_pass) {
   std::vector<std::tuple<std::string, int32_t, int32_t>> out(pairs.size());
   if (pairs.empty()) {
     return out;
   }
   AlignerBatch batch(0, 4ull << 30, band_width);
   batch.set_band_policy(policy);
+  batch.set_wide_pass(wide_pass);
   size_t begin = 0;
   std::vector<int32_t> slots(pairs.size(), -1);
   auto flush = [&](size_t end) {
@@ -616,7 +625,7 @@ std::vector<std::tuple<std::vector<std::pair<uint32_t, uint32_t>>, int32_t, int3
 breaking_points_pairs(const std::vector<std::pair<std::string, std::string>>& pairs,
                       uint32_t window_length, const std::vector<uint32_t>& t_begins,
                       const std::vector<uint32_t>& q_begins, uint32_t band_width,
-                      AlnBandPolicy policy) {
+                      AlnBandPolicy policy, bool wide_pass) {
   if (window_length == 0) {
     throw std::invalid_argument("breaking_points_pairs: window_length must be positive");
   }
@@ -631,6 +640,7 @@ breaking_points_pairs(const std::vector<std::pair<std::string, std::string>>& pa
   }
   AlignerBatch batch(0, 4ull << 30, band_width);
   batch.set_band_policy(policy);
+  batch.set_wide_pass(wide_pass);
   size_t begin = 0;
   std::vector<int32_t> slots(pairs.size(), -1);
   auto flush = [&](size_t end) {

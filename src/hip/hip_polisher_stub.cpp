@@ -53,14 +53,15 @@ poa_window_graph_gpu(
   exit(1);
 }
 std::vector<std::tuple<std::string, int32_t, int32_t>> align_pairs(
-    const std::vector<std::pair<std::string, std::string>>&, uint32_t, AlnBandPolicy) {
+    const std::vector<std::pair<std::string, std::string>>&, uint32_t, AlnBandPolicy,
+    bool) {
   fprintf(stderr, "[rga::hip::align_pairs] error: no HIP backend in this build!\n");
   exit(1);
 }
 std::vector<std::tuple<std::vector<std::pair<uint32_t, uint32_t>>, int32_t, int32_t>>
 breaking_points_pairs(const std::vector<std::pair<std::string, std::string>>&, uint32_t,
                       const std::vector<uint32_t>&, const std::vector<uint32_t>&, uint32_t,
-                      AlnBandPolicy) {
+                      AlnBandPolicy, bool) {
   fprintf(stderr, "[rga::hip::breaking_points_pairs] error: no HIP backend in this build!\n");
   exit(1);
 }

@@ -28,12 +28,12 @@ int runtime_device_count();  // provided by the HIP backend (or the stub)
 void runtime_device_synchronize();
 std::vector<std::tuple<std::string, int32_t, int32_t>> align_pairs(
     const std::vector<std::pair<std::string, std::string>>& pairs, uint32_t band_width,
-    AlnBandPolicy policy);
+    AlnBandPolicy policy, bool wide_pass);
 std::vector<std::tuple<std::vector<std::pair<uint32_t, uint32_t>>, int32_t, int32_t>>
 breaking_points_pairs(const std::vector<std::pair<std::string, std::string>>& pairs,
                       uint32_t window_length, const std::vector<uint32_t>& t_begins,
                       const std::vector<uint32_t>& q_begins, uint32_t band_width,
-                      AlnBandPolicy policy);
+                      AlnBandPolicy policy, bool wide_pass);
 std::vector<std::pair<std::string, bool>> poa_windows_gpu(
     const std::vector<std::vector<std::tuple<std::string, std::string, uint32_t, uint32_t>>>&
         window_layers,
@@ -54,7 +54,8 @@ std::vector<std::pair<std::string, std::string>> polish(
     const std::string& target_path, bool fragment_correction, uint32_t window_length,
     double quality_threshold, double error_threshold, bool trim, int8_t match, int8_t mismatch,
     int8_t gap, uint32_t threads, uint32_t poa_batches, bool banded_poa, uint32_t aligner_batches,
-    uint32_t aligner_band_width, bool include_unpolished, bool aligner_adaptive_band) {
+    uint32_t aligner_band_width, bool include_unpolished, bool aligner_adaptive_band,
+    bool aligner_wide_band) {
   rga::PolisherConfig config;
   config.type = fragment_correction ? rga::PolisherType::kF : rga::PolisherType::kC;
   config.window_length = window_length;
@@ -70,6 +71,7 @@ std::vector<std::pair<std::string, std::string>> polish(
   config.aligner_batches = aligner_batches;
   config.aligner_band_width = aligner_band_width;
   config.aligner_adaptive_band = aligner_adaptive_band;
+  config.aligner_wide_band = aligner_wide_band;
 
   std::vector<std::pair<std::string, std::string>> result;
   {
@@ -92,8 +94,10 @@ rga::hip::AlnBandPolicy band_policy_of(const std::string& name) {
   if (name == "diagonal") return rga::hip::AlnBandPolicy::kDiagonal;
   if (name == "adaptive") return rga::hip::AlnBandPolicy::kAdaptive;
   if (name == "retry") return rga::hip::AlnBandPolicy::kRetry;
-  throw py::value_error("band_policy must be \"diagonal\", \"adaptive\" or \"retry\", not \"" +
-                        name + "\"");
+  if (name == "wide") return rga::hip::AlnBandPolicy::kWide;
+  throw py::value_error(
+      "band_policy must be \"diagonal\", \"adaptive\", \"retry\" or \"wide\", not \"" + name +
+      "\"");
 }
 
 int64_t edit_distance_py(const std::string& a, const std::string& b) {
@@ -243,7 +247,7 @@ PYBIND11_MODULE(_racon, m) {
         py::arg("gap") = -4, py::arg("threads") = 1, py::arg("poa_batches") = 0,
         py::arg("banded_poa") = false, py::arg("aligner_batches") = 0,
         py::arg("aligner_band_width") = 0, py::arg("include_unpolished") = false,
-        py::arg("aligner_adaptive_band") = false,
+        py::arg("aligner_adaptive_band") = false, py::arg("aligner_wide_band") = false,
         "Polish targets with reads+overlaps; returns [(name, sequence)].");
 
   m.def("device_count", [] { return rga::hip::runtime_device_count(); },
@@ -288,29 +292,32 @@ PYBIND11_MODULE(_racon, m) {
   m.def("edit_distance", &edit_distance_py, py::arg("a"), py::arg("b"));
   m.def("align_cigar", &align_cigar_py, py::arg("query"), py::arg("target"));
   m.def("gpu_align", [](const std::vector<std::pair<std::string, std::string>>& pairs,
-                        uint32_t band_width, const std::string& band_policy) {
+                        uint32_t band_width, const std::string& band_policy, bool wide_pass) {
           const rga::hip::AlnBandPolicy policy = band_policy_of(band_policy);
           py::gil_scoped_release release;
-          return rga::hip::align_pairs(pairs, band_width, policy);
+          return rga::hip::align_pairs(pairs, band_width, policy, wide_pass);
         },
         py::arg("pairs"), py::arg("band_width") = 0, py::arg("band_policy") = "diagonal",
+        py::kw_only(), py::arg("wide_pass") = false,
         "GPU Myers aligner on raw (query, target) pairs -> (cigar, edit_distance, status). "
-        "band_policy: \"diagonal\", \"adaptive\" (the band follows the scores) or \"retry\" "
-        "(diagonal, then adaptive over the pairs that escaped)");
+        "band_policy: \"diagonal\", \"adaptive\" (the band follows the scores), \"retry\" "
+        "(diagonal, then adaptive over the pairs that escaped) or \"wide\" (one wavefront per "
+        "pair, band 4096, whatever band_width). wide_pass: the pairs that the policy leaves "
+        "escaped go through the wide band last");
   m.def("gpu_breaking_points",
         [](const std::vector<std::pair<std::string, std::string>>& pairs, uint32_t window_length,
            const std::optional<std::vector<uint32_t>>& t_begins,
            const std::optional<std::vector<uint32_t>>& q_begins, uint32_t band_width,
-           const std::string& band_policy) {
+           const std::string& band_policy, bool wide_pass) {
           const rga::hip::AlnBandPolicy policy = band_policy_of(band_policy);
           py::gil_scoped_release release;
           return rga::hip::breaking_points_pairs(
               pairs, window_length, t_begins.value_or(std::vector<uint32_t>()),
-              q_begins.value_or(std::vector<uint32_t>()), band_width, policy);
+              q_begins.value_or(std::vector<uint32_t>()), band_width, policy, wide_pass);
         },
         py::arg("pairs"), py::arg("window_length"), py::arg("t_begins") = py::none(),
         py::arg("q_begins") = py::none(), py::arg("band_width") = 0,
-        py::arg("band_policy") = "diagonal",
+        py::arg("band_policy") = "diagonal", py::kw_only(), py::arg("wide_pass") = false,
         "GPU Myers aligner in breaking-point mode on raw (query, target) pairs whose "
         "target / query start at t_begins[k] / q_begins[k] -> ([(t, q), ...], "
         "edit_distance, status)");

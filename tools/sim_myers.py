@@ -153,6 +153,160 @@ def align(q, t, K, adaptive=False):
     return ed, "".join(reversed(path)), "ok"
 
 
+WAVE_K = 64  # blocks of the wave kernel's band: one per lane
+
+
+def wave_single_slide(n, m):
+    """True when the diagonal rule at K = 64 never slides more than one block
+    per column. The wave schedule needs that (a new block takes its state from
+    the lane above, one step earlier); the host refuses the other pairs, which
+    need n > 64 m."""
+    if n <= 64 * m:
+        return True  # the band centre moves at most 64 rows per column
+    nbt = (n + 63) >> 6
+    return all(btop_of(j, n, m, nbt, WAVE_K) - btop_of(j - 1, n, m, nbt, WAVE_K) <= 1
+               for j in range(1, m + 1))
+
+
+def align_wave(q, t):
+    """Schedule model of src/hip/aligner_wave_kernel.hip: one wavefront per
+    alignment, lane = one 64-row block of a 64-block band. Returns exactly
+    align(q, t, 64) for every pair wave_single_slide() admits, and
+    (None, None, "refused") for the others.
+
+    Block B of column j is computed at step s = j + B by lane B & 63, so both
+    of its inputs are one step old: (B - 1, j) on the lane above, (B, j - 1) on
+    the lane itself. When the band's top passes block B its lane idles for 64
+    steps and comes back as block B + 64, which starts pessimistic from the
+    score the lane above hands over. Column states are stored by step,
+    [s][lane], and the traceback reads that store."""
+    K = WAVE_K
+    n, m = len(q), len(t)
+    if not wave_single_slide(n, m):
+        return None, None, "refused"
+    nbt = (n + 63) >> 6
+
+    def top(j):
+        return btop_of(j, n, m, nbt, K)
+
+    def masks_of(B):  # a lane builds its block's Eq masks from q when it takes it over
+        eq = [0] * 4
+        for k in range(min(64, n - B * 64) if B < nbt else 0):
+            c = base_code(q[B * 64 + k])
+            if c < 4:
+                eq[c] |= 1 << k
+        return eq
+
+    steps = m + 64 + nbt + 1  # rows of the store; the last one written is m + top(m) + 63
+    store = [[None] * K for _ in range(steps)]
+    blk = list(range(K))  # block each lane owns
+    eqs = [masks_of(B) for B in blk]
+    Pv = [M64] * K
+    Mv = [0] * K
+    S = [(B + 1) * 64 for B in blk]
+    for lane in range(K):  # column 0: block B at step B
+        store[lane][lane] = (Pv[lane], Mv[lane], S[lane])
+    hout_reg = [0] * K  # what each lane sent at the end of the step before
+    s_reg = [0] * K
+
+    def recycle(lane, s):
+        """After step s: the band's top passes the lane's block before the
+        lane's next column, so the lane takes over the block 64 below."""
+        B = blk[lane]
+        jn = s + 1 - B
+        if 1 <= jn <= m and B < top(jn):
+            blk[lane] = B + K
+            eqs[lane] = masks_of(B + K)
+
+    last = m + top(m) + K - 1
+    assert last < steps
+    # step 0 computes nothing, but it has its recycle: with top(1) = 1 block 0
+    # leaves the band before its first column (t_len = 1 and 4097..4160 rows,
+    # 4224 x 2, ...) and lane 0 starts as block 64
+    for lane in range(K):
+        recycle(lane, 0)
+    for s in range(1, last + 1):
+        hin_in = [hout_reg[(lane - 1) % K] for lane in range(K)]  # one lane up
+        s_in = [s_reg[(lane - 1) % K] for lane in range(K)]
+        for lane in range(K):
+            B = blk[lane]
+            j = s - B
+            if 1 <= j <= m:
+                bt = top(j)
+                assert B >= bt  # recycled in time
+                if B <= bt + K - 1:
+                    if B > top(j - 1) + K - 1:  # the block enters the band here
+                        Pv[lane], Mv[lane] = M64, 0
+                        S[lane] = (s_in[lane] - hin_in[lane]) + 64  # S_above(j - 1) + 64
+                    hin = 1 if B == bt else hin_in[lane]
+                    c = base_code(t[j - 1])
+                    Eq = eqs[lane][c] if c < 4 else 0
+                    hin_neg = 1 if hin < 0 else 0
+                    hin_pos = 1 if hin > 0 else 0
+                    Xv = Eq | Mv[lane]
+                    Eq |= hin_neg
+                    Xh = ((((Eq & Pv[lane]) + Pv[lane]) & M64) ^ Pv[lane]) | Eq
+                    Ph = Mv[lane] | (~(Xh | Pv[lane]) & M64)
+                    Mh = Pv[lane] & Xh
+                    hout = ((Ph >> 63) & 1) - ((Mh >> 63) & 1)
+                    Ph = ((Ph << 1) | hin_pos) & M64
+                    Mh = ((Mh << 1) | hin_neg) & M64
+                    Pv[lane] = Mh | (~(Xv | Ph) & M64)
+                    Mv[lane] = Ph & Xv
+                    S[lane] += hout
+                    hout_reg[lane], s_reg[lane] = hout, S[lane]
+                    assert store[s][lane] is None
+                    store[s][lane] = (Pv[lane], Mv[lane], S[lane])
+            recycle(lane, s)
+
+    Bf = (n - 1) >> 6
+    rb = Bf - top(m)
+    if rb < 0 or rb >= K:
+        return None, None, "bandedge-final"
+    assert blk[Bf % K] == Bf
+    D = score_at(S[Bf % K], Pv[Bf % K], Mv[Bf % K], (n - 1) & 63)
+    ed = D
+
+    def state(B, j):  # None when (B, j) is outside the band
+        if j < 0 or j > m or not (top(j) <= B <= top(j) + K - 1):
+            return None
+        return store[j + B][B % K]
+
+    path = []
+    i, j = n, m
+    while i > 0 and j > 0:
+        B = (i - 1) >> 6
+        k = (i - 1) & 63
+        sj, sj1 = state(B, j), state(B, j - 1)
+        if sj is None or sj1 is None:
+            return ed, None, "bandedge-tb"
+        Pvj, Mvj, _ = sj
+        Pvj1, Mvj1, S1 = sj1
+        vd = 1 if (Pvj >> k) & 1 else (-1 if (Mvj >> k) & 1 else 0)
+        D_left = score_at(S1, Pvj1, Mvj1, k)
+        vd1 = 1 if (Pvj1 >> k) & 1 else (-1 if (Mvj1 >> k) & 1 else 0)
+        D_diag = D_left - vd1
+        sub = 0 if (base_code(q[i - 1]) == base_code(t[j - 1]) and base_code(q[i - 1]) < 4) else 1
+        if D_diag + sub == D:
+            path.append("M")
+            i -= 1
+            j -= 1
+            D = D_diag
+        elif D_left + 1 == D:
+            path.append("D")
+            j -= 1
+            D = D_left
+        elif vd == 1:
+            path.append("I")
+            i -= 1
+            D = D - vd
+        else:
+            return ed, None, "stuck"
+    path.extend("I" * i)
+    path.extend("D" * j)
+    return ed, "".join(reversed(path)), "ok"
+
+
 def check_path(q, t, path, ed):
     qi = ti = cost = 0
     for op in path:
@@ -225,6 +379,31 @@ def main():
         else:
             check_path(q, t, apath, aed)
             a_exact += aed == ref
+        # the wave schedule is the diagonal band at K = 64, nothing else
+        if align_wave(q, t) != align(q, t, WAVE_K):
+            print(f"FAIL trial {trial}: align_wave differs at n={len(q)} m={m}")
+            fails += 1
+    # queries of more than 4096 rows, where the wave schedule recycles lanes
+    for trial in range(max(1, trials // 20)):
+        m = rng.randint(2000, 6000)
+        t = "".join(rng.choice("ACGT") for _ in range(m))
+        q = mutate(t, rng, rng.choice([0.02, 0.15]))
+        q = q[:len(q) // 2] + "".join(rng.choice("ACGT") for _ in range(rng.randint(0, 3000))) \
+            + q[len(q) // 2:]
+        if align_wave(q, t) != align(q, t, WAVE_K):
+            print(f"FAIL long trial {trial}: align_wave differs at n={len(q)} m={m}")
+            fails += 1
+    # tiny targets under queries just above the band: the band's top moves at
+    # column 1 or 2, before some lanes have computed anything
+    for trial in range(max(3, trials // 5)):
+        m = rng.randint(1, 3)
+        n = rng.randint(4097, 4097 + 64 * m + 63)
+        q = "".join(rng.choice("ACGT") for _ in range(n))
+        t = "".join(rng.choice("ACGT") for _ in range(m))
+        want = align(q, t, WAVE_K) if wave_single_slide(n, m) else (None, None, "refused")
+        if align_wave(q, t) != want:
+            print(f"FAIL tiny-target trial {trial}: align_wave differs at n={n} m={m}")
+            fails += 1
     print(f"K={K}: {trials} trials, {fails} fails, {edges} band-edge (diagonal), "
           f"{a_edges} band-edge / {a_exact} optimal (adaptive)")
     return 1 if fails else 0
