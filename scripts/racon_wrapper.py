@@ -8,7 +8,7 @@ with concatenated stdout. Two deliberate improvements over the reference:
 
 * GPU flags (-c/--cudapoa-batches, --cudaaligner-batches,
   -b/--cuda-banded-alignment, --cudaaligner-band-width,
-  --aligner-adaptive-band, --aligner-wide-band) are ACTUALLY
+  --aligner-adaptive-band, --aligner-wide-band, --poa-large-graphs) are ACTUALLY
   forwarded to racon; the reference parses but drops them
   (racon_wrapper.py:38-40,130-131 are commented out there).
 * binaries are located at runtime (RACON_BIN / RAMPLER_BIN env vars, then
@@ -85,6 +85,9 @@ def main():
     parser.add_argument("--aligner-wide-band", action="store_true",
                         help="last GPU pass, one wavefront per overlap with a band of "
                              "4096, over overlaps that are still escaped")
+    parser.add_argument("--poa-large-graphs", action="store_true",
+                        help="second GPU pass, in slabs of 4095 nodes, over windows "
+                             "whose POA graph outgrows the GPU's node cap")
     parser.add_argument("--in-process", action="store_true",
                         help="polish every --split chunk inside ONE process via the "
                              "_racon module instead of one racon subprocess per chunk: "
@@ -152,7 +155,8 @@ def main():
                     aligner_band_width=int(args.cudaaligner_band_width),
                     include_unpolished=args.include_unpolished,
                     aligner_adaptive_band=args.aligner_adaptive_band,
-                    aligner_wide_band=args.aligner_wide_band)
+                    aligner_wide_band=args.aligner_wide_band,
+                    poa_large_graphs=args.poa_large_graphs)
                 for name, seq in out:
                     sys.stdout.write(f">{name}\n{seq}\n")
                 sys.stdout.flush()
@@ -180,6 +184,8 @@ def main():
             cmd.append("--aligner-adaptive-band")
         if args.aligner_wide_band:
             cmd.append("--aligner-wide-band")
+        if args.poa_large_graphs:
+            cmd.append("--poa-large-graphs")
         cmd += [sequences, overlaps, None]
 
         for chunk in chunks:

@@ -18,6 +18,7 @@ constexpr int32_t kAlignerBatchesOpt = 10000;
 constexpr int32_t kAlignerBandWidthOpt = 10001;
 constexpr int32_t kAlignerAdaptiveBandOpt = 10002;
 constexpr int32_t kAlignerWideBandOpt = 10003;
+constexpr int32_t kPoaLargeGraphsOpt = 10004;
 
 struct option long_options[] = {
     {"include-unpolished", no_argument, nullptr, 'u'},
@@ -38,6 +39,7 @@ struct option long_options[] = {
     {"cudaaligner-band-width", required_argument, nullptr, kAlignerBandWidthOpt},
     {"aligner-adaptive-band", no_argument, nullptr, kAlignerAdaptiveBandOpt},
     {"aligner-wide-band", no_argument, nullptr, kAlignerWideBandOpt},
+    {"poa-large-graphs", no_argument, nullptr, kPoaLargeGraphsOpt},
     {nullptr, 0, nullptr, 0}};
 
 void help() {
@@ -108,7 +110,11 @@ void help() {
       "            give overlaps that are still escaped a last pass on the GPU, one\n"
       "            wavefront per overlap with a band of 4096, before the CPU aligner\n"
       "            takes them (independent of --aligner-adaptive-band; no effect\n"
-      "            without --cudaaligner-batches)\n");
+      "            without --cudaaligner-batches)\n"
+      "        --poa-large-graphs\n"
+      "            give windows whose POA graph outgrows the GPU's node cap a second\n"
+      "            pass on the GPU, in slabs of 4095 nodes, before the CPU engine\n"
+      "            takes them (no effect without -c)\n");
 }
 
 }  // namespace
@@ -148,6 +154,7 @@ int main(int argc, char** argv) {
       case kAlignerBandWidthOpt: config.aligner_band_width = atoi(optarg); break;
       case kAlignerAdaptiveBandOpt: config.aligner_adaptive_band = true; break;
       case kAlignerWideBandOpt: config.aligner_wide_band = true; break;
+      case kPoaLargeGraphsOpt: config.poa_large_graphs = true; break;
       default: exit(1);
     }
   }

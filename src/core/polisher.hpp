@@ -53,6 +53,10 @@ struct PolisherConfig {
   // wavefront per overlap with a band of 4096 (hip::AlnBandPolicy::kWide's
   // kernel). Off by default; independent of aligner_adaptive_band.
   bool aligner_wide_band = false;
+  // second GPU pass for windows whose POA graph outgrows the device's node
+  // cap: they run again in slabs of twice the capacity (4095 nodes) before
+  // the CPU engine takes what is left (HIP POA batches only). Off by default.
+  bool poa_large_graphs = false;
 };
 
 class Polisher {

@@ -65,17 +65,22 @@ void release_aligner(int device, uint32_t band, std::unique_ptr<hip::AlignerBatc
   p.aligner.emplace_back(key, std::move(b));
 }
 
-uint64_t poa_key(int device, int8_t m, int8_t x, int8_t g, bool banded, uint32_t depth) {
+// depth stays below 2^14 (the device caps it at 200); a batch with a large
+// slab pool is another batch than one without
+uint64_t poa_key(int device, int8_t m, int8_t x, int8_t g, bool banded, uint32_t depth,
+                 bool large_graphs) {
   return (static_cast<uint64_t>(device) << 40) |
          (static_cast<uint64_t>(static_cast<uint8_t>(m)) << 32) |
          (static_cast<uint64_t>(static_cast<uint8_t>(x)) << 24) |
          (static_cast<uint64_t>(static_cast<uint8_t>(g)) << 16) |
-         (static_cast<uint64_t>(banded) << 15) | depth;
+         (static_cast<uint64_t>(banded) << 15) | (static_cast<uint64_t>(large_graphs) << 14) |
+         depth;
 }
 
 std::unique_ptr<hip::PoaBatch> acquire_poa(int device, size_t budget, int8_t m, int8_t x,
-                                           int8_t g, bool banded, uint32_t depth) {
-  const uint64_t key = poa_key(device, m, x, g, banded, depth);
+                                           int8_t g, bool banded, uint32_t depth,
+                                           bool large_graphs) {
+  const uint64_t key = poa_key(device, m, x, g, banded, depth, large_graphs);
   auto& p = pools();
   {
     std::lock_guard<std::mutex> lock(p.mutex);
@@ -87,7 +92,7 @@ std::unique_ptr<hip::PoaBatch> acquire_poa(int device, size_t budget, int8_t m, 
       }
     }
   }
-  return std::make_unique<hip::PoaBatch>(device, budget, m, x, g, banded, depth);
+  return std::make_unique<hip::PoaBatch>(device, budget, m, x, g, banded, depth, large_graphs);
 }
 
 void release_poa(uint64_t key, std::unique_ptr<hip::PoaBatch> b) {
@@ -292,7 +297,8 @@ class HipPolisher : public Polisher {
       // thresholds must match the PoaBatch constructor guard exactly: the
       // kernel clamps stored scores at -28000 in every mode, and banded mode
       // reserves values below that as out-of-band sentinels
-      if (static_cast<int32_t>(2047 + 1024) * worst_param >
+      if (static_cast<int32_t>(hip::kPoaLimits.max_nodes + hip::kPoaLimits.matrix_width) *
+              worst_param >
           (config_.banded_poa ? 27000 : 28000)) {
         fprintf(stderr,
                 "[rga::HipPolisher] warning: score parameters too large for the "
@@ -300,6 +306,17 @@ class HipPolisher : public Polisher {
         Polisher::polish(dst, drop_unpolished);
         return;
       }
+    }
+
+    // the large-graph pass has a score guard of its own (its graphs are
+    // twice as deep); where it fails the run goes on without the pass
+    bool large_graphs = config_.poa_large_graphs;
+    if (large_graphs && !hip::PoaBatch::large_scores_fit(config_.match, config_.mismatch,
+                                                         config_.gap, config_.banded_poa)) {
+      fprintf(stderr,
+              "[rga::HipPolisher] warning: score parameters too large for the int16 "
+              "scores of the large-graph pass; running without it\n");
+      large_graphs = false;
     }
 
     logger_->log();
@@ -316,9 +333,10 @@ class HipPolisher : public Polisher {
         size_t budget = static_cast<size_t>(free_mem * mem_fraction()) / config_.poa_batches;
         for (uint32_t b = 0; b < config_.poa_batches; ++b) {
           batches.emplace_back(acquire_poa(d, budget, config_.match, config_.mismatch,
-                                           config_.gap, config_.banded_poa, kMaxDepth));
+                                           config_.gap, config_.banded_poa, kMaxDepth,
+                                           large_graphs));
           batch_keys.emplace_back(poa_key(d, config_.match, config_.mismatch, config_.gap,
-                                          config_.banded_poa, kMaxDepth));
+                                          config_.banded_poa, kMaxDepth, large_graphs));
         }
       }
     } catch (const std::exception& e) {
@@ -338,6 +356,7 @@ class HipPolisher : public Polisher {
     uint64_t next_window = 0;
     std::mutex status_mutex;
     std::atomic<int64_t> t_fill_ns{0}, t_gpu_ns{0};
+    std::atomic<uint64_t> large_completed{0};
 
     auto worker = [&](hip::PoaBatch* batch) {
       using clk = std::chrono::steady_clock;
@@ -386,6 +405,7 @@ class HipPolisher : public Polisher {
           return;
         }
         auto status = batch->generate(config_.trim);
+        large_completed += batch->large_completed();
         t_gpu_ns += (clk::now() - t1).count();
         {
           std::lock_guard<std::mutex> lock(status_mutex);
@@ -413,6 +433,10 @@ class HipPolisher : public Polisher {
             "[rga::HipPolisher] poa timings: queue %.3f s, pack+gpu+post %.3f s "
             "(sum over %zu batch threads)\n",
             t_fill_ns.load() / 1e9, t_gpu_ns.load() / 1e9, threads.size());
+    if (large_completed.load() > 0) {
+      fprintf(stderr, "[rga::HipPolisher] %lu window(s) completed by the large-graph pass\n",
+              static_cast<unsigned long>(large_completed.load()));
+    }
 
     // CPU fallback for every window the GPU did not polish
     // (reference cudapolisher.cpp:354-383)
@@ -441,6 +465,16 @@ class HipPolisher : public Polisher {
 
 namespace hip {
 int runtime_device_count() { return device_count(); }
+
+// Frees the pooled batches (and with them their device and pinned memory):
+// for long-lived processes that are done polishing for a while, and for
+// tests that need the memory the pools of earlier runs still hold.
+void release_batch_pools() {
+  auto& p = pools();
+  std::lock_guard<std::mutex> lock(p.mutex);
+  p.aligner.clear();
+  p.poa.clear();
+}
 
 void runtime_device_synchronize() { RGA_HIP_CHECK(hipDeviceSynchronize()); }
 
@@ -484,12 +518,13 @@ static std::vector<std::shared_ptr<Window>> windows_from_layers(const RawWindows
 std::vector<std::pair<std::string, bool>> poa_windows_gpu(
     const std::vector<std::vector<std::tuple<std::string, std::string, uint32_t, uint32_t>>>&
         window_layers,
-    int8_t match, int8_t mismatch, int8_t gap, bool banded, bool trim, bool tgs) {
+    int8_t match, int8_t mismatch, int8_t gap, bool banded, bool trim, bool tgs,
+    bool large_graphs) {
   std::vector<std::pair<std::string, bool>> out(window_layers.size());
   std::vector<std::shared_ptr<Window>> windows =
       windows_from_layers(window_layers, tgs, "poa_windows_gpu");
 
-  hip::PoaBatch batch(0, 4ull << 30, match, mismatch, gap, banded, 200);
+  hip::PoaBatch batch(0, 4ull << 30, match, mismatch, gap, banded, 200, large_graphs);
   size_t begin = 0;
   std::vector<int64_t> slot_of(windows.size(), -1);
   auto flush = [&](size_t end) {
@@ -539,10 +574,10 @@ std::vector<std::pair<std::string, bool>> poa_windows_gpu(
 // (< 3 layers, backbone too long) or that do not fit one batch.
 std::vector<std::tuple<int32_t, std::vector<uint16_t>, std::vector<std::vector<uint16_t>>>>
 poa_window_graph_gpu(const RawWindows& window_layers, int8_t match, int8_t mismatch, int8_t gap,
-                     bool banded) {
+                     bool banded, bool large_graphs) {
   std::vector<std::shared_ptr<Window>> windows =
       windows_from_layers(window_layers, true, "poa_window_graph_gpu");
-  hip::PoaBatch batch(0, 4ull << 30, match, mismatch, gap, banded, 200);
+  hip::PoaBatch batch(0, 4ull << 30, match, mismatch, gap, banded, 200, large_graphs);
   for (const auto& w : windows) {
     bool never_fits = false;
     if (w->num_layers() < 3 || !batch.add_window(w, &never_fits)) {

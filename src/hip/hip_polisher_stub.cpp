@@ -12,6 +12,7 @@
 #include "core/polisher.hpp"
 #include "hip/aligner_types.hpp"
 #include "hip/comm.hpp"
+#include "hip/poa_types.hpp"  // host-only: its layout static_asserts hold in this build too
 
 namespace rga {
 
@@ -39,16 +40,17 @@ Communicator& world_comm() {
 namespace hip {
 int runtime_device_count() { return 0; }
 void runtime_device_synchronize() {}
+void release_batch_pools() {}
 std::vector<std::pair<std::string, bool>> poa_windows_gpu(
     const std::vector<std::vector<std::tuple<std::string, std::string, uint32_t, uint32_t>>>&,
-    int8_t, int8_t, int8_t, bool, bool, bool) {
+    int8_t, int8_t, int8_t, bool, bool, bool, bool) {
   fprintf(stderr, "[rga::hip::poa_windows_gpu] error: no HIP backend in this build!\n");
   exit(1);
 }
 std::vector<std::tuple<int32_t, std::vector<uint16_t>, std::vector<std::vector<uint16_t>>>>
 poa_window_graph_gpu(
     const std::vector<std::vector<std::tuple<std::string, std::string, uint32_t, uint32_t>>>&,
-    int8_t, int8_t, int8_t, bool) {
+    int8_t, int8_t, int8_t, bool, bool) {
   fprintf(stderr, "[rga::hip::poa_window_graph_gpu] error: no HIP backend in this build!\n");
   exit(1);
 }

@@ -17,11 +17,28 @@ namespace {
 constexpr size_t kSeqArenaPerWindow = 96 * 1024;  // bases+weights staging per window (avg)
 
 constexpr PoaLimits L = kPoaLimits;
+constexpr PoaLimits LL = kPoaLargeLimits;  // the large-graph pass's class
+
+// Large pool rule (docs/DESIGN.md, "Large-graph pass"): a quarter of the
+// batch's memory budget, at most the 2048 windows that can be resident at
+// once (256 CUs x 8 workgroups of 20 KiB LDS), at least one.
+constexpr size_t kLargeBudgetDivisor = 4;
+constexpr size_t kLargeSlabCap = 2048;
+constexpr size_t kLargePerWindow =
+    poa_slab_bytes<true>() + LL.max_consensus * 3 + sizeof(PoaWindowDesc) + 1024;
 
 }  // namespace
 
+bool PoaBatch::large_scores_fit(int8_t match, int8_t mismatch, int8_t gap, bool banded) {
+  const int32_t worst = static_cast<int32_t>(LL.max_nodes + LL.matrix_width) *
+                        std::max({std::abs(static_cast<int32_t>(match)),
+                                  std::abs(static_cast<int32_t>(mismatch)),
+                                  std::abs(static_cast<int32_t>(gap))});
+  return worst <= (banded ? 27000 : 28000);
+}
+
 PoaBatch::PoaBatch(int device, size_t mem_budget, int8_t match, int8_t mismatch, int8_t gap,
-                   bool banded, uint32_t max_depth)
+                   bool banded, uint32_t max_depth, bool large_graphs)
     : device_(device), match_(match), mismatch_(mismatch), gap_(gap), max_depth_(max_depth) {
   // int16 score guard: worst |score| <= (max_nodes + matrix_width) * max|param|
   // (banded mode additionally reserves values below -28000 as out-of-band)
@@ -41,10 +58,34 @@ PoaBatch::PoaBatch(int device, size_t mem_budget, int8_t match, int8_t mismatch,
     throw std::runtime_error(msg);
   }
 
+  if (large_graphs && !large_scores_fit(match, mismatch, gap, banded)) {
+    fprintf(stderr,
+            "[rga::hip::PoaBatch] warning: score parameters too large for the int16 scores "
+            "of the large-graph pass ((%u+%u)*max > %d); the pass is off for this batch\n",
+            LL.max_nodes, LL.matrix_width, banded ? 27000 : 28000);
+    large_graphs = false;
+  }
+
   RGA_HIP_TRY(hipSetDevice(device_));
   hipStream_t s;
   RGA_HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
   stream_ = s;
+
+  // the large pool comes out of the budget before the regular slabs are
+  // counted. RGA_POA_LARGE_SLABS is a test knob that sets its size directly
+  // (a small pool forces sub-launches), held to the same cap and to half of
+  // the budget so that the regular batch keeps the other half.
+  if (large_graphs) {
+    size_t n = std::min(kLargeSlabCap, mem_budget / kLargeBudgetDivisor / kLargePerWindow);
+    const char* e = getenv("RGA_POA_LARGE_SLABS");
+    const long v = e != nullptr ? atol(e) : 0;
+    if (v > 0) {
+      n = std::min({static_cast<size_t>(v), kLargeSlabCap, mem_budget / 2 / kLargePerWindow});
+    }
+    large_slabs_ = static_cast<uint32_t>(std::max<size_t>(1, n));
+    const size_t taken = static_cast<size_t>(large_slabs_) * kLargePerWindow;
+    mem_budget = mem_budget > taken ? mem_budget - taken : 0;
+  }
 
   const size_t per_window = poa_slab_bytes() + kSeqArenaPerWindow +
                             L.max_consensus * 3 + sizeof(PoaWindowDesc) + 1024;
@@ -115,6 +156,9 @@ void PoaBatch::allocate_arenas(bool banded) {
       throw std::runtime_error(
           "[rga::hip::PoaBatch] device arena allocation failed (out of memory)");
     }
+    if (large_slabs_ > 1) {
+      large_slabs_ /= 2;  // memory is short: the pool to come shrinks with the batch
+    }
   }
 
   // ---- pinned host staging, sized to the slab count that fit ----
@@ -137,6 +181,66 @@ void PoaBatch::allocate_arenas(bool banded) {
   arena_.mismatch = mismatch_;
   arena_.gap = gap_;
   arena_.band_width = banded ? 256 : 0;  // reference static band 256
+
+  if (large_slabs_ != 0) {
+    allocate_large_pool();
+  }
+}
+
+// ---- the large-graph pass's pool: large-class slabs with descriptors,
+// timing and outputs of their own, in one allocation next to the regular
+// one. The packed inputs are shared with arena_. Degrades on OOM as the
+// regular pool does.
+void PoaBatch::allocate_large_pool() {
+  large_arena_ = arena_;  // inputs, scores and band; the rest is carved below
+  auto lay_out = [&](void* base) {
+    size_t total = 0;
+    auto carve = [&](auto*& p, size_t count) {
+      p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(
+          reinterpret_cast<uintptr_t>(base) + total);
+      total += (count * sizeof(*p) + 255) & ~size_t(255);
+    };
+    const size_t slabs = large_slabs_;
+    carve(large_arena_.layer_ends_index, slabs + 1);
+    carve(large_arena_.windows, slabs);
+    for_each_poa_slab<true>(large_arena_.slabs,
+                            [&](auto*& p, size_t count) { carve(p, slabs * count); });
+    carve(large_arena_.timing, slabs * kPoaTimingSlots);
+    carve(large_arena_.consensus, slabs * LL.max_consensus);
+    carve(large_arena_.coverage, slabs * LL.max_consensus);
+    carve(large_arena_.consensus_len, slabs);
+    carve(large_arena_.status, slabs);
+    carve(large_arena_.num_nodes, slabs);
+    return total;
+  };
+  for (;; large_slabs_ /= 2) {
+    if (large_slabs_ == 0) {
+      // not worth failing the batch for: the regular path is complete without
+      fprintf(stderr,
+              "[rga::hip::PoaBatch] warning: no memory for a large-graph slab; the "
+              "large-graph pass is off for this batch\n");
+      return;
+    }
+    hipError_t err = hipMalloc(&d_large_pool_, lay_out(nullptr));
+    if (err == hipSuccess) {
+      break;
+    }
+    d_large_pool_ = nullptr;
+    (void)hipGetLastError();  // clear the sticky OOM
+  }
+  lay_out(d_large_pool_);
+
+  const size_t n = large_slabs_;
+  RGA_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h_large_desc_),
+                            n * sizeof(PoaWindowDesc)));
+  RGA_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h_large_layer_index_), n * 4));
+  RGA_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h_large_consensus_),
+                            n * LL.max_consensus));
+  RGA_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h_large_coverage_),
+                            n * LL.max_consensus * 2));
+  RGA_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h_large_consensus_len_), n * 4));
+  RGA_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h_large_status_), n * 4));
+  RGA_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h_large_num_nodes_), n * 4));
 }
 
 PoaBatch::~PoaBatch() { release_all(); }
@@ -145,6 +249,17 @@ void PoaBatch::release_all() {
   (void)hipSetDevice(device_);
   if (d_pool_ != nullptr) {
     (void)hipFree(d_pool_);
+  }
+  if (d_large_pool_ != nullptr) {
+    (void)hipFree(d_large_pool_);
+  }
+  for (void* p : {static_cast<void*>(h_large_desc_), static_cast<void*>(h_large_layer_index_),
+                  static_cast<void*>(h_large_consensus_), static_cast<void*>(h_large_coverage_),
+                  static_cast<void*>(h_large_consensus_len_),
+                  static_cast<void*>(h_large_status_), static_cast<void*>(h_large_num_nodes_)}) {
+    if (p != nullptr) {
+      (void)hipHostFree(p);
+    }
   }
   for (void* p : {static_cast<void*>(h_seq_), static_cast<void*>(h_weight_),
                   static_cast<void*>(h_layer_ends_), static_cast<void*>(h_layer_span_),
@@ -339,6 +454,23 @@ std::vector<bool> PoaBatch::generate(bool trim) {
   RGA_HIP_CHECK(hipStreamSynchronize(s));
   auto t2 = clk::now();
 
+  // second chance for the windows that outgrew their variant's node cap
+  large_completed_ = 0;
+  large_slab_of_.assign(nw, -1);
+  large_nodes_of_.assign(nw, 0);
+  auto t_post = t2;  // where the post-processing share of the host timing starts
+  if (large_slabs_ != 0) {
+    const uint32_t ran = run_large_pass();
+    t_post = clk::now();
+    if (host_timing && ran != 0) {
+      fprintf(stderr,
+              "[rga::hip::PoaBatch] host timing: large-graph pass over %u window(s) %.1f ms\n",
+              ran,
+              std::chrono::duration_cast<std::chrono::microseconds>(t_post - t2).count() /
+                  1000.0);
+    }
+  }
+
   if (getenv("RGA_POA_TIMING") != nullptr) {
     constexpr size_t kSlots = kPoaTimingSlots;
     std::vector<unsigned long long> t(nw * kSlots);
@@ -395,6 +527,9 @@ std::vector<bool> PoaBatch::generate(bool trim) {
     }
     if (status) {
       window->set_consensus(std::move(consensus));
+      if (large_slab_of_[i] >= 0) {
+        ++large_completed_;
+      }
     }
     polished[orig] = status;
   }
@@ -406,9 +541,104 @@ std::vector<bool> PoaBatch::generate(bool trim) {
     fprintf(stderr,
             "[rga::hip::PoaBatch] host timing (%zu windows): pack+sort+h2d+launch %.1f ms, "
             "gpu sync %.1f ms, post %.1f ms\n",
-            nw, ms(t0, t1), ms(t1, t2), ms(t2, t3));
+            nw, ms(t0, t1), ms(t1, t2), ms(t_post, t3));
   }
   return polished;
+}
+
+// The windows the regular launches left with kPoaNodeOverflow, again, in the
+// large slabs. Runs after the status copy of generate(): h_desc_ and
+// h_layer_index_ hold the sorted (kernel slot) order and the packed inputs
+// are on the device, so a window only needs a descriptor that names a large
+// slab. The kernel builds its graph from the backbone up, whatever the slab
+// held. Status, consensus, coverage and node count of every window of the
+// pass replace those of its kernel slot, so the post-processing of generate()
+// treats it like any other. Only kPoaNodeOverflow is retried: the other caps
+// are the same in both classes.
+uint32_t PoaBatch::run_large_pass() {
+  const size_t nw = windows_.size();
+  std::vector<uint32_t> todo;
+  for (uint32_t i = 0; i < nw; ++i) {
+    if (h_status_[i] == kPoaNodeOverflow) {
+      todo.push_back(i);
+    }
+  }
+  if (todo.empty()) {
+    return 0;
+  }
+  // heaviest first, as in the regular launches
+  auto cost = [&](uint32_t slot) {
+    return h_layer_ends_[h_layer_index_[slot] + h_desc_[slot].num_seqs - 1];
+  };
+  std::sort(todo.begin(), todo.end(), [&](uint32_t a, uint32_t b) {
+    const uint32_t ca = cost(a), cb = cost(b);
+    return ca != cb ? ca > cb : a < b;
+  });
+
+  auto s = static_cast<hipStream_t>(stream_);
+  const bool timing = getenv("RGA_POA_TIMING") != nullptr;
+  large_slab_owner_.assign(large_slabs_, -1);
+  for (size_t begin = 0; begin < todo.size(); begin += large_slabs_) {
+    const uint32_t n = static_cast<uint32_t>(std::min<size_t>(large_slabs_, todo.size() - begin));
+    for (uint32_t k = 0; k < n; ++k) {
+      const uint32_t slot = todo[begin + k];
+      h_large_desc_[k] = h_desc_[slot];
+      h_large_desc_[k].scratch_idx = k;
+      h_large_layer_index_[k] = h_layer_index_[slot];
+    }
+    RGA_HIP_CHECK(hipMemcpyAsync(const_cast<PoaWindowDesc*>(large_arena_.windows), h_large_desc_,
+                                 n * sizeof(PoaWindowDesc), hipMemcpyHostToDevice, s));
+    RGA_HIP_CHECK(hipMemcpyAsync(const_cast<uint32_t*>(large_arena_.layer_ends_index),
+                                 h_large_layer_index_, n * 4, hipMemcpyHostToDevice, s));
+    launch_poa_kernel_large(large_arena_, 0, n, stream_);
+    RGA_HIP_CHECK(hipMemcpyAsync(h_large_consensus_, large_arena_.consensus,
+                                 static_cast<size_t>(n) * LL.max_consensus,
+                                 hipMemcpyDeviceToHost, s));
+    RGA_HIP_CHECK(hipMemcpyAsync(h_large_coverage_, large_arena_.coverage,
+                                 static_cast<size_t>(n) * LL.max_consensus * 2,
+                                 hipMemcpyDeviceToHost, s));
+    RGA_HIP_CHECK(hipMemcpyAsync(h_large_consensus_len_, large_arena_.consensus_len, n * 4,
+                                 hipMemcpyDeviceToHost, s));
+    RGA_HIP_CHECK(hipMemcpyAsync(h_large_status_, large_arena_.status, n * 4,
+                                 hipMemcpyDeviceToHost, s));
+    RGA_HIP_CHECK(hipMemcpyAsync(h_large_num_nodes_, large_arena_.num_nodes, n * 4,
+                                 hipMemcpyDeviceToHost, s));
+    RGA_HIP_CHECK(hipStreamSynchronize(s));
+
+    static_assert(L.max_consensus == LL.max_consensus);
+    for (uint32_t k = 0; k < n; ++k) {
+      const uint32_t slot = todo[begin + k];
+      h_status_[slot] = h_large_status_[k];
+      h_consensus_len_[slot] = h_large_consensus_len_[k];
+      std::memcpy(h_consensus_ + static_cast<size_t>(slot) * L.max_consensus,
+                  h_large_consensus_ + static_cast<size_t>(k) * LL.max_consensus,
+                  LL.max_consensus);
+      std::memcpy(h_coverage_ + static_cast<size_t>(slot) * L.max_consensus,
+                  h_large_coverage_ + static_cast<size_t>(k) * LL.max_consensus,
+                  LL.max_consensus * 2);
+      large_slab_of_[slot] = static_cast<int32_t>(k);
+      large_nodes_of_[slot] = h_large_num_nodes_[k];
+      large_slab_owner_[k] = slot;
+    }
+
+    if (timing) {
+      constexpr size_t kSlots = kPoaTimingSlots;
+      std::vector<unsigned long long> t(n * kSlots);
+      RGA_HIP_CHECK(hipMemcpy(t.data(), large_arena_.timing, t.size() * sizeof(t[0]),
+                              hipMemcpyDeviceToHost));
+      unsigned long long sum[kSlots] = {0};
+      unsigned long long longest = 0;
+      for (size_t i = 0; i < n; ++i) {
+        for (size_t k = 0; k < kSlots; ++k) sum[k] += t[i * kSlots + k];
+        longest = std::max(longest, t[i * kSlots + 6]);
+      }
+      fprintf(stderr,
+              "[rga::hip::PoaBatch] large-graph pass timing (wall ticks, %u windows): dp=%llu "
+              "tb=%llu add=%llu topo=%llu rdesc=%llu cons=%llu total=%llu layers=%llu max=%llu\n",
+              n, sum[0], sum[1], sum[2], sum[3], sum[4], sum[5], sum[6], sum[7], longest);
+    }
+  }
+  return static_cast<uint32_t>(todo.size());
 }
 
 PoaBatch::WindowGraph PoaBatch::read_graph(uint32_t index) const {
@@ -422,22 +652,41 @@ PoaBatch::WindowGraph PoaBatch::read_graph(uint32_t index) const {
     return g;
   }
   uint32_t n = 0;
-  RGA_HIP_CHECK(hipMemcpy(&n, arena_.num_nodes + launch_slot_[index], sizeof(n),
-                          hipMemcpyDeviceToHost));
-  if (n > L.max_nodes) {
-    throw std::runtime_error("[rga::hip::PoaBatch] read_graph: node count beyond the slab");
+  const PoaSlabs* slabs = &arena_.slabs;
+  size_t slab = 0;  // first node of the window's slab
+  const uint32_t slot = launch_slot_[index];
+  if (slot < large_slab_of_.size() && large_slab_of_[slot] >= 0) {
+    // finished in the large-graph pass: the graph is in its large slab
+    const uint32_t k = static_cast<uint32_t>(large_slab_of_[slot]);
+    if (large_slab_owner_[k] != static_cast<int64_t>(slot)) {
+      throw std::runtime_error(
+          "[rga::hip::PoaBatch] read_graph: a later sub-launch of the large-graph pass "
+          "reused the window's slab");
+    }
+    n = large_nodes_of_[slot];
+    if (n > LL.max_nodes) {
+      throw std::runtime_error("[rga::hip::PoaBatch] read_graph: node count beyond the slab");
+    }
+    slabs = &large_arena_.slabs;
+    slab = static_cast<size_t>(k) * LL.max_nodes;
+  } else {
+    RGA_HIP_CHECK(hipMemcpy(&n, arena_.num_nodes + slot, sizeof(n), hipMemcpyDeviceToHost));
+    if (n > L.max_nodes) {
+      throw std::runtime_error("[rga::hip::PoaBatch] read_graph: node count beyond the slab");
+    }
+    // add_window gave window `index` the slab of the same number
+    slab = static_cast<size_t>(index) * L.max_nodes;
   }
-  // add_window gave window `index` the slab of the same number
-  const size_t slab = static_cast<size_t>(index) * L.max_nodes;
+  static_assert(L.max_edges == LL.max_edges);
   g.rank.resize(n);
   g.out_cnt.resize(n);
   g.out_edges.resize(static_cast<size_t>(n) * L.max_edges);
   if (n != 0) {
-    RGA_HIP_CHECK(hipMemcpy(g.rank.data(), arena_.slabs.rank + slab, n * sizeof(uint16_t),
+    RGA_HIP_CHECK(hipMemcpy(g.rank.data(), slabs->rank + slab, n * sizeof(uint16_t),
                             hipMemcpyDeviceToHost));
-    RGA_HIP_CHECK(hipMemcpy(g.out_cnt.data(), arena_.slabs.out_cnt + slab, n,
+    RGA_HIP_CHECK(hipMemcpy(g.out_cnt.data(), slabs->out_cnt + slab, n,
                             hipMemcpyDeviceToHost));
-    RGA_HIP_CHECK(hipMemcpy(g.out_edges.data(), arena_.slabs.out_edges + slab * L.max_edges,
+    RGA_HIP_CHECK(hipMemcpy(g.out_edges.data(), slabs->out_edges + slab * L.max_edges,
                             g.out_edges.size() * sizeof(uint16_t), hipMemcpyDeviceToHost));
   }
   return g;
@@ -445,6 +694,9 @@ PoaBatch::WindowGraph PoaBatch::read_graph(uint32_t index) const {
 
 void PoaBatch::reset() {
   launch_slot_.clear();
+  large_slab_of_.clear();
+  large_nodes_of_.clear();
+  large_completed_ = 0;
   windows_.clear();
   seqs_added_.clear();
   pending_orders_.clear();

@@ -17,8 +17,12 @@ namespace rga::hip {
 
 class PoaBatch {
  public:
+  // large_graphs: carve a pool of large-class slabs (kPoaLargeLimits) out of
+  // the budget and give the windows that end with kPoaNodeOverflow a second
+  // pass in them (docs/DESIGN.md, "Large-graph pass"). Off, the batch is what
+  // it was without the option: no pool, the same slab count.
   PoaBatch(int device, size_t mem_budget, int8_t match, int8_t mismatch, int8_t gap,
-           bool banded, uint32_t max_depth);
+           bool banded, uint32_t max_depth, bool large_graphs = false);
   ~PoaBatch();
 
   PoaBatch(const PoaBatch&) = delete;
@@ -38,6 +42,15 @@ class PoaBatch {
   uint32_t size() const { return static_cast<uint32_t>(windows_.size()); }
   uint32_t capacity() const { return num_slabs_; }
 
+  // int16 score guard of the large class: (4095 + 1024) * max(|m|,|x|,|g|)
+  // within the bound the regular class is held to. A batch asked for large
+  // graphs with scores that fail it warns once and runs without the pass.
+  static bool large_scores_fit(int8_t match, int8_t mismatch, int8_t gap, bool banded);
+  // large slabs of this batch; 0 when the pass is off
+  uint32_t large_capacity() const { return large_slabs_; }
+  // windows of the last generate() that the large-graph pass completed
+  uint32_t large_completed() const { return large_completed_; }
+
   // Runs the kernel and writes consensus into the windows; returns per-window
   // polish status (false = needs CPU fallback or <3-layer backbone copy).
   std::vector<bool> generate(bool trim);
@@ -45,7 +58,9 @@ class PoaBatch {
   // Test and debugging entry, not used by the polishing path: the graph that
   // the last generate() left in the slab of window `index` (add_window
   // order). Every window of a batch has a slab of its own until reset().
-  // For a window that did not end with kPoaOk only the status is set.
+  // For a window that did not end with kPoaOk only the status is set. A
+  // window completed by the large-graph pass is read from its large slab,
+  // which it keeps unless a later sub-launch of the pass needed the slab.
   struct WindowGraph {
     int32_t status = kPoaNotRun;
     std::vector<uint16_t> rank;       // node -> topological rank
@@ -60,7 +75,12 @@ class PoaBatch {
   // Constructor phases (see .cpp): OOM-degrading arena allocation and the
   // matching cleanup used by both the destructor and a throwing constructor.
   void allocate_arenas(bool banded);
+  void allocate_large_pool();
   void release_all();
+  // second pass of generate(): the kPoaNodeOverflow windows through the large
+  // slabs, results merged into the windows' kernel slots; returns how many
+  // windows it ran
+  uint32_t run_large_pass();
 
   int device_;
   void* stream_ = nullptr;
@@ -93,6 +113,26 @@ class PoaBatch {
   std::vector<std::vector<uint32_t>> pending_orders_;  // layer order per reserved window
   size_t packed_upto_ = 0;
   std::vector<uint32_t> launch_slot_;  // last generate(): kernel slot per window
+
+  // ---- large-graph pass (all empty / null when the option is off) ----
+  uint32_t large_slabs_ = 0;
+  void* d_large_pool_ = nullptr;
+  // shares the packed inputs of arena_; descriptors, slabs, timing and
+  // outputs are the pool's own, indexed by large slab
+  PoaDeviceArena large_arena_{};
+  PoaWindowDesc* h_large_desc_ = nullptr;
+  uint32_t* h_large_layer_index_ = nullptr;
+  uint8_t* h_large_consensus_ = nullptr;
+  uint16_t* h_large_coverage_ = nullptr;
+  uint32_t* h_large_consensus_len_ = nullptr;
+  int32_t* h_large_status_ = nullptr;
+  uint32_t* h_large_num_nodes_ = nullptr;
+  uint32_t large_completed_ = 0;
+  // last generate(), per kernel slot: the large slab the window ran in (-1:
+  // not in the pass) and the node count it ended with
+  std::vector<int32_t> large_slab_of_;
+  std::vector<uint32_t> large_nodes_of_;
+  std::vector<int64_t> large_slab_owner_;  // per large slab: kernel slot of its last user
 };
 
 }  // namespace rga::hip

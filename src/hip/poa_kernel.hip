@@ -45,10 +45,22 @@ namespace {
 
 constexpr int kLanes = 64;
 constexpr int32_t kNegInf = -(1 << 28);
-constexpr uint32_t kMaxW = kPoaLimits.matrix_width;   // DP row width (slab and widest ring)
-constexpr uint32_t kMaxN = kPoaLimits.max_nodes + 1;  // widest LDS Kahn arrays
-constexpr uint32_t kMaxE = kPoaLimits.max_edges;
-constexpr uint32_t kMaxR = kPoaLimits.max_ring;
+// Capacity class of this translation unit. The source is compiled once per
+// class: as it stands for the regular one (kPoaLimits), and through
+// poa_kernel_large.hip, which defines RGA_POA_LARGE_CLASS and includes this
+// file, for the large one (kPoaLargeLimits). Everything below is inside the
+// unnamed namespace, so the two copies do not meet; only the launch function
+// at the end has a name per class.
+#ifdef RGA_POA_LARGE_CLASS
+constexpr bool kLarge = true;
+#else
+constexpr bool kLarge = false;
+#endif
+constexpr PoaLimits kL = poa_limits(kLarge);
+constexpr uint32_t kMaxW = kL.matrix_width;   // DP row width (slab and widest ring)
+constexpr uint32_t kMaxN = kL.max_nodes + 1;  // widest LDS Kahn arrays
+constexpr uint32_t kMaxE = kL.max_edges;
+constexpr uint32_t kMaxR = kL.max_ring;
 constexpr uint32_t kRing = 4;     // DP rows kept in LDS
 constexpr uint32_t kMaxPre = 5;   // predecessor rows carried by the row descriptors
 // Minus infinity of a multi-predecessor row, whose candidates are compared as
@@ -131,10 +143,16 @@ static_assert(kMaxPre == 5, "row_desc2 holds four 16-bit rows");
 // Kahn out-adjacency word (Shared::kahn.adj): first out-edge target in the
 // low 11 bits (node ids stop at max_nodes - 1 < 2048), out-degree above it,
 // saturating at kAdjSat (a saturated word sends the FIFO to out_cnt).
-constexpr uint32_t kAdjBits = 11;
+// The large class needs a twelfth bit of node id and takes it from the
+// degree, 12 + 4 saturating at 15, so the word stays 16 bits: a 32-bit word
+// would grow the kahn side from 20 to 28 KiB and cost three of the eight
+// resident workgroups per CU, while a node with 15 or more out-edges only
+// costs the FIFO one more global load.
+constexpr uint32_t kAdjBits = kLarge ? 12 : 11;
 constexpr uint32_t kAdjMask = (1u << kAdjBits) - 1;
-constexpr uint32_t kAdjSat = 31;
-static_assert(kPoaLimits.max_nodes <= kAdjMask + 1, "node id does not fit the adjacency word");
+constexpr uint32_t kAdjSat = (1u << (16 - kAdjBits)) - 1;
+static_assert(kAdjSat == (kLarge ? 15u : 31u));
+static_assert(kL.max_nodes <= kAdjMask + 1, "node id does not fit the adjacency word");
 
 // LDS block state — cross-batch window co-residency is the dominant
 // throughput lever (a 19 KB variant with full graph-array mirrors made each
@@ -475,7 +493,7 @@ __device__ void topo_sort_d(WindowCtx& c, SH& s, int lane) {
         nout = c.out_cnt[u];
       }
       // edge rows are 96 bytes from a 256-byte aligned base: 16-byte loads
-      static_assert(kMaxE % 8 == 0 && (kPoaLimits.max_nodes * kMaxE * 2) % 16 == 0);
+      static_assert(kMaxE % 8 == 0 && (kL.max_nodes * kMaxE * 2) % 16 == 0);
       const uint16_t* row = c.out_edges + u * kMaxE;
       for (uint32_t base = 0; base < nout; base += 8) {
         const uint4 v4 = *reinterpret_cast<const uint4*>(row + base);
@@ -1161,14 +1179,19 @@ __device__ __forceinline__ void dp_row(const WindowCtx c, SH& s, const LayerDp& 
       // from the owning lane's last value. (Missing this for ANY
       // multiple-of-8 row length left ring[len] uninitialized and made
       // results depend on stale LDS — caught by tools/probe_order.py.)
-      const uint32_t rem = len > base ? len - base : 0;
+      // The large class is the one 8-wide variant that runs banded rows
+      // (the route gives the regular classes' banded windows to the 5-wide
+      // variants): there the last covered column is the band's, jend, which
+      // is always a multiple of 8 and a valid column of the row (pred_band).
+      const uint32_t tail_col = kLarge ? jend : len;
+      const uint32_t rem = tail_col > base ? tail_col - base : 0;
       if (rem > 0 && rem <= kLanes * WB && (rem & (WB - 1)) == 0) {
         const int owner = static_cast<int>(rem / WB) - 1;
         const int32_t t16 = __builtin_amdgcn_readlane(harr[WB - 1], owner);
         if (lane == 0) {
-          ring_row[len] = static_cast<int16_t>(t16);
+          ring_row[tail_col] = static_cast<int16_t>(t16);
           if (store_row) {
-            Hrow[len] = static_cast<int16_t>(t16);
+            Hrow[tail_col] = static_cast<int16_t>(t16);
           }
         }
       }
@@ -1389,7 +1412,8 @@ __global__ void poa_window_kernel(PoaDeviceArena a, uint32_t window_base,
 
   WindowCtx c;
   static_cast<PoaSlabs&>(c) = a.slabs;
-  for_each_poa_slab(c, [slab = static_cast<size_t>(desc.scratch_idx)](auto*& p, size_t count) {
+  for_each_poa_slab<kLarge>(c, [slab = static_cast<size_t>(desc.scratch_idx)](auto*& p,
+                                                                              size_t count) {
     p += slab * count;
   });
 
@@ -1526,12 +1550,12 @@ __global__ void poa_window_kernel(PoaDeviceArena a, uint32_t window_base,
 
   // ---- consensus ----
   if (lane == 0) {
-    uint8_t* out = a.consensus + static_cast<size_t>(win) * kPoaLimits.max_consensus;
-    uint16_t* cov = a.coverage + static_cast<size_t>(win) * kPoaLimits.max_consensus;
+    uint8_t* out = a.consensus + static_cast<size_t>(win) * kL.max_consensus;
+    uint16_t* cov = a.coverage + static_cast<size_t>(win) * kL.max_consensus;
     int32_t clen = -1;
     (void)lap();
     if (c.status == kPoaOk) {
-      clen = consensus_d(c, s, out, cov, kPoaLimits.max_consensus);
+      clen = consensus_d(c, s, out, cov, kL.max_consensus);
     }
     t_cons = lap();
     a.consensus_len[win] = clen < 0 ? 0 : static_cast<uint32_t>(clen);
@@ -1558,6 +1582,30 @@ __global__ void poa_window_kernel(PoaDeviceArena a, uint32_t window_base,
 // window) beats a 9-wide single-pass variant by ~8% — non-power-of-two
 // unrolls lose more in generated address code than the extra, mostly
 // empty pass costs. The ring width (LDS) sets occupancy; see Shared<W>.
+#ifdef RGA_POA_LARGE_CLASS
+// the large class has the one variant
+template <bool TIMED>
+void launch_large(const PoaDeviceArena& arena, uint32_t window_base, uint32_t num_windows,
+                  hipStream_t stream) {
+  constexpr PoaVariantParams p = kPoaLargeVariant;
+  hipLaunchKernelGGL(
+      (poa_window_kernel<TIMED, p.cols_per_lane, p.ring_width, p.node_cap, p.min_waves>),
+      dim3(num_windows), dim3(kLanes), 0, stream, arena, window_base, num_windows);
+}
+
+}  // namespace
+
+void launch_poa_kernel_large(const PoaDeviceArena& arena, uint32_t window_base,
+                             uint32_t num_windows, void* stream) {
+  static const bool timed = getenv("RGA_POA_TIMING") != nullptr;
+  auto st = static_cast<hipStream_t>(stream);
+  if (timed) {
+    launch_large<true>(arena, window_base, num_windows, st);
+  } else {
+    launch_large<false>(arena, window_base, num_windows, st);
+  }
+}
+#else
 template <bool TIMED, PoaVariant V>
 void launch_variant(const PoaDeviceArena& arena, uint32_t window_base, uint32_t num_windows,
                     hipStream_t stream) {
@@ -1598,5 +1646,6 @@ void launch_poa_kernel(const PoaDeviceArena& arena, uint32_t window_base,
     dispatch_variant<false>(arena, window_base, num_windows, variant, st);
   }
 }
+#endif  // RGA_POA_LARGE_CLASS
 
 }  // namespace rga::hip

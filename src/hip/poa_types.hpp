@@ -29,6 +29,19 @@ struct PoaLimits {
 };
 inline constexpr PoaLimits kPoaLimits{};
 
+// Second capacity class, for the opt-in large-graph pass over the windows
+// that end with kPoaNodeOverflow (PoaBatch, docs/DESIGN.md "Large-graph
+// pass"): twice the nodes, everything else as above. Node ids, ranks and
+// descriptor rows are 16-bit fields and hold it; the slabs and the kernel are
+// compiled once per class (poa_kernel.hip, poa_kernel_large.hip).
+inline constexpr PoaLimits kPoaLargeLimits{4095, 48, 4, 1024, 2048};
+constexpr PoaLimits poa_limits(bool large) { return large ? kPoaLargeLimits : kPoaLimits; }
+static_assert(kPoaLargeLimits.max_edges == kPoaLimits.max_edges &&
+                  kPoaLargeLimits.max_ring == kPoaLimits.max_ring &&
+                  kPoaLargeLimits.matrix_width == kPoaLimits.matrix_width &&
+                  kPoaLargeLimits.max_consensus == kPoaLimits.max_consensus,
+              "the classes differ in max_nodes alone: they share inputs and outputs");
+
 // Window status codes produced by the kernel.
 enum PoaStatus : int32_t {
   kPoaOk = 0,
@@ -59,6 +72,14 @@ struct PoaVariantParams {
   uint32_t node_cap;       // LDS Kahn capacity; the graph holds node_cap - 1
   uint32_t min_waves;      // waves/SIMD the compiler budgets registers for
 };
+
+// The large class has one kernel variant, full width, taking banded rows at
+// run time as kPoaFull does. LDS: the Kahn side is 5 B per node, 20 KiB,
+// which is 8 workgroups per CU, two waves per SIMD.
+inline constexpr PoaVariantParams kPoaLargeVariant = {8, kPoaLargeLimits.matrix_width,
+                                                      kPoaLargeLimits.max_nodes + 1, 2};
+static_assert(5 * kPoaLargeVariant.node_cap * (4 * kPoaLargeVariant.min_waves) <= 160 * 1024,
+              "the large variant's Kahn side must leave min_waves waves per SIMD resident");
 
 inline constexpr PoaVariantParams kPoaVariants[kPoaNumVariants] = {
     {5, 384, kPoaLimits.max_nodes + 1, 4},                      // kPoaNarrow
@@ -168,11 +189,11 @@ struct PoaSlabs {
 #undef RGA_X
 };
 
-// calls f(pointer member, elements per window) for every slab array, in
-// allocation order
-template <class F>
+// calls f(pointer member, elements per window) for every slab array of the
+// capacity class, in allocation order
+template <bool LARGE = false, class F>
 constexpr void for_each_poa_slab(PoaSlabs& s, F&& f) {
-  constexpr PoaLimits L = kPoaLimits;
+  constexpr PoaLimits L = poa_limits(LARGE);
   constexpr size_t N = L.max_nodes;
 #define RGA_X(T, name, count) f(s.name, static_cast<size_t>(count));
   RGA_POA_SLAB_ARRAYS(RGA_X)
@@ -182,13 +203,16 @@ constexpr void for_each_poa_slab(PoaSlabs& s, F&& f) {
 constexpr size_t kPoaTimingSlots = 8;
 
 // device scratch bytes one window needs (unrounded; sizes the batch)
+template <bool LARGE = false>
 constexpr size_t poa_slab_bytes() {
   PoaSlabs s{};
   size_t b = kPoaTimingSlots * sizeof(unsigned long long);
-  for_each_poa_slab(s, [&b](auto* p, size_t count) { b += count * sizeof(*p); });
+  for_each_poa_slab<LARGE>(s, [&b](auto* p, size_t count) { b += count * sizeof(*p); });
   return b;
 }
 static_assert(poa_slab_bytes() == 7200396, "slab layout changed: batch sizes move with it");
+static_assert(poa_slab_bytes<true>() == 14384780,
+              "large slab layout changed: the large pool's size moves with it");
 
 // Device arena pointers (one allocation, carved into slabs).
 struct PoaDeviceArena {
@@ -233,5 +257,10 @@ struct PoaDeviceArena {
 // num_windows) of the (variant-sorted) desc array.
 void launch_poa_kernel(const PoaDeviceArena& arena, uint32_t window_base,
                        uint32_t num_windows, PoaVariant variant, void* stream);
+
+// The same for an arena of large-class slabs (kPoaLargeLimits), which has
+// the one variant kPoaLargeVariant.
+void launch_poa_kernel_large(const PoaDeviceArena& arena, uint32_t window_base,
+                             uint32_t num_windows, void* stream);
 
 }  // namespace rga::hip

@@ -26,6 +26,7 @@
 namespace rga::hip {
 int runtime_device_count();  // provided by the HIP backend (or the stub)
 void runtime_device_synchronize();
+void release_batch_pools();
 std::vector<std::tuple<std::string, int32_t, int32_t>> align_pairs(
     const std::vector<std::pair<std::string, std::string>>& pairs, uint32_t band_width,
     AlnBandPolicy policy, bool wide_pass);
@@ -37,12 +38,13 @@ breaking_points_pairs(const std::vector<std::pair<std::string, std::string>>& pa
 std::vector<std::pair<std::string, bool>> poa_windows_gpu(
     const std::vector<std::vector<std::tuple<std::string, std::string, uint32_t, uint32_t>>>&
         window_layers,
-    int8_t match, int8_t mismatch, int8_t gap, bool banded, bool trim, bool tgs);
+    int8_t match, int8_t mismatch, int8_t gap, bool banded, bool trim, bool tgs,
+    bool large_graphs);
 std::vector<std::tuple<int32_t, std::vector<uint16_t>, std::vector<std::vector<uint16_t>>>>
 poa_window_graph_gpu(
     const std::vector<std::vector<std::tuple<std::string, std::string, uint32_t, uint32_t>>>&
         window_layers,
-    int8_t match, int8_t mismatch, int8_t gap, bool banded);
+    int8_t match, int8_t mismatch, int8_t gap, bool banded, bool large_graphs);
 }
 
 namespace py = pybind11;
@@ -55,7 +57,7 @@ std::vector<std::pair<std::string, std::string>> polish(
     double quality_threshold, double error_threshold, bool trim, int8_t match, int8_t mismatch,
     int8_t gap, uint32_t threads, uint32_t poa_batches, bool banded_poa, uint32_t aligner_batches,
     uint32_t aligner_band_width, bool include_unpolished, bool aligner_adaptive_band,
-    bool aligner_wide_band) {
+    bool aligner_wide_band, bool poa_large_graphs) {
   rga::PolisherConfig config;
   config.type = fragment_correction ? rga::PolisherType::kF : rga::PolisherType::kC;
   config.window_length = window_length;
@@ -72,6 +74,7 @@ std::vector<std::pair<std::string, std::string>> polish(
   config.aligner_band_width = aligner_band_width;
   config.aligner_adaptive_band = aligner_adaptive_band;
   config.aligner_wide_band = aligner_wide_band;
+  config.poa_large_graphs = poa_large_graphs;
 
   std::vector<std::pair<std::string, std::string>> result;
   {
@@ -248,6 +251,7 @@ PYBIND11_MODULE(_racon, m) {
         py::arg("banded_poa") = false, py::arg("aligner_batches") = 0,
         py::arg("aligner_band_width") = 0, py::arg("include_unpolished") = false,
         py::arg("aligner_adaptive_band") = false, py::arg("aligner_wide_band") = false,
+        py::arg("poa_large_graphs") = false,
         "Polish targets with reads+overlaps; returns [(name, sequence)].");
 
   m.def("device_count", [] { return rga::hip::runtime_device_count(); },
@@ -256,6 +260,11 @@ PYBIND11_MODULE(_racon, m) {
     py::gil_scoped_release release;
     rga::hip::runtime_device_synchronize();
   });
+
+  m.def("release_batch_pools", [] {
+    py::gil_scoped_release release;
+    rga::hip::release_batch_pools();
+  }, "Frees the GPU batch arenas that polish() keeps pooled between calls.");
 
   // distributed communicator (hip/comm.hpp): TCP control plane + RCCL data
   // plane; one process per GPU
@@ -336,24 +345,25 @@ PYBIND11_MODULE(_racon, m) {
   m.def("poa_windows_gpu", [](const std::vector<std::vector<
                                   std::tuple<std::string, std::string, uint32_t, uint32_t>>>& w,
                               int8_t match, int8_t mismatch, int8_t gap, bool banded,
-                              bool trim, bool tgs) {
+                              bool trim, bool tgs, bool large_graphs) {
     py::gil_scoped_release release;
-    return rga::hip::poa_windows_gpu(w, match, mismatch, gap, banded, trim, tgs);
+    return rga::hip::poa_windows_gpu(w, match, mismatch, gap, banded, trim, tgs, large_graphs);
   }, py::arg("windows"), py::arg("match") = 3, py::arg("mismatch") = -5,
      py::arg("gap") = -4, py::arg("banded") = false, py::arg("trim") = true,
-     py::arg("tgs") = true);
+     py::arg("tgs") = true, py::arg("large_graphs") = false);
   m.def("poa_window_graph_gpu",
         [](const std::vector<
                std::vector<std::tuple<std::string, std::string, uint32_t, uint32_t>>>& w,
-           int8_t match, int8_t mismatch, int8_t gap, bool banded) {
+           int8_t match, int8_t mismatch, int8_t gap, bool banded, bool large_graphs) {
           py::gil_scoped_release release;
-          return rga::hip::poa_window_graph_gpu(w, match, mismatch, gap, banded);
+          return rga::hip::poa_window_graph_gpu(w, match, mismatch, gap, banded, large_graphs);
         },
         py::arg("windows"), py::arg("match") = 3, py::arg("mismatch") = -5, py::arg("gap") = -4,
-        py::arg("banded") = false,
+        py::arg("banded") = false, py::arg("large_graphs") = false,
         "Test entry: the windows through the GPU POA kernel in one batch, then per window "
         "(status, rank per node, out-edge targets per node) read back from its slab; the "
-        "lists are empty unless status is 0.");
+        "lists are empty unless status is 0. large_graphs: with the large-graph pass, whose "
+        "windows are read back from their large slabs.");
   m.def("poa_consensus", &poa_consensus, py::arg("sequences"),
         py::arg("qualities") = std::vector<std::string>(), py::arg("match") = 5,
         py::arg("mismatch") = -4, py::arg("gap") = -8);
