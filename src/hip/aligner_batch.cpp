@@ -67,6 +67,12 @@ void AlignerBatch::allocate_arenas(size_t mem_budget) {
   // On OOM (shared-device setups) the pool halves and retries.
   size_t pool = std::min<size_t>(mem_budget, 12ull << 30);
   size_t total = 0;
+  // Every arena starts on a 256-byte boundary and owns a multiple of 256
+  // bytes. The lane kernel relies on that for the sequence arena: it reads
+  // sequences in aligned 8-byte words, and the word that holds the last
+  // sequence byte of a fill may extend up to 7 bytes past seq_bytes_, which
+  // the rounding keeps inside the carve whatever seq_cap_ is (no slack is
+  // taken from reserve_span's capacity check).
   auto carve = [&total](size_t bytes) {
     size_t off = total;
     total += (bytes + 255) & ~size_t(255);
