@@ -8,8 +8,8 @@ with concatenated stdout. Two deliberate improvements over the reference:
 
 * GPU flags (-c/--cudapoa-batches, --cudaaligner-batches,
   -b/--cuda-banded-alignment, --cudaaligner-band-width,
-  --aligner-adaptive-band, --aligner-wide-band, --poa-large-graphs) are ACTUALLY
-  forwarded to racon; the reference parses but drops them
+  --aligner-adaptive-band, --aligner-wide-band, --poa-large-graphs,
+  --poa-score-check) are ACTUALLY forwarded to racon; the reference parses but drops them
   (racon_wrapper.py:38-40,130-131 are commented out there).
 * binaries are located at runtime (RACON_BIN / RAMPLER_BIN env vars, then
   the in-tree build/ directory, then PATH) instead of CMake path
@@ -88,6 +88,9 @@ def main():
     parser.add_argument("--poa-large-graphs", action="store_true",
                         help="second GPU pass, in slabs of 4095 nodes, over windows "
                              "whose POA graph outgrows the GPU's node cap")
+    parser.add_argument("--poa-score-check", action="store_true",
+                        help="per-window int16 score range check on the GPU in place of "
+                             "the worst-case guard on the score parameters")
     parser.add_argument("--in-process", action="store_true",
                         help="polish every --split chunk inside ONE process via the "
                              "_racon module instead of one racon subprocess per chunk: "
@@ -156,7 +159,8 @@ def main():
                     include_unpolished=args.include_unpolished,
                     aligner_adaptive_band=args.aligner_adaptive_band,
                     aligner_wide_band=args.aligner_wide_band,
-                    poa_large_graphs=args.poa_large_graphs)
+                    poa_large_graphs=args.poa_large_graphs,
+                    poa_score_check=args.poa_score_check)
                 for name, seq in out:
                     sys.stdout.write(f">{name}\n{seq}\n")
                 sys.stdout.flush()
@@ -186,6 +190,8 @@ def main():
             cmd.append("--aligner-wide-band")
         if args.poa_large_graphs:
             cmd.append("--poa-large-graphs")
+        if args.poa_score_check:
+            cmd.append("--poa-score-check")
         cmd += [sequences, overlaps, None]
 
         for chunk in chunks:

@@ -377,7 +377,7 @@ void Graph::update_alignment(Alignment* alignment, const std::vector<int32_t>& m
   }
 }
 
-Alignment NWEngine::align(const char* seq, uint32_t len, const Graph& graph) {
+Alignment NWEngine::align(const char* seq, uint32_t len, const Graph& graph, ScoreStats* stats) {
   Alignment alignment;
   if (graph.nodes().empty() || len == 0) {
     return alignment;
@@ -456,6 +456,18 @@ Alignment NWEngine::align(const char* seq, uint32_t len, const Graph& graph) {
         max_i = r + 1;
       }
     }
+  }
+
+  if (stats != nullptr) {
+    for (uint32_t i = 1; i < height; ++i) {
+      stats->check_min =
+          std::min<int64_t>(stats->check_min, H_[static_cast<size_t>(i) * width] +
+                                                  static_cast<int64_t>(len) * gap_);
+    }
+    const auto range =
+        std::minmax_element(H_.begin(), H_.begin() + static_cast<size_t>(width) * height);
+    stats->true_min = std::min<int64_t>(stats->true_min, *range.first);
+    stats->true_max = std::max<int64_t>(stats->true_max, *range.second);
   }
 
   // Backtrack from (max_i, len): spoa move priority is diagonal (predecessors

@@ -80,6 +80,17 @@ class Graph {
   uint32_t num_sequences_ = 0;
 };
 
+// Score range of the DP matrices of one or more alignments, gathered on
+// request (NWEngine::align): the CPU model of the HIP engine's per-window
+// score check (hip/poa_types.hpp). check_min is the smallest H[row][0] + len *
+// gap over the graph rows, which is what the device compares with its floor;
+// true_min and true_max are the smallest and largest cells.
+struct ScoreStats {
+  int64_t check_min = INT64_MAX;
+  int64_t true_min = INT64_MAX;
+  int64_t true_max = INT64_MIN;
+};
+
 // Linear-gap Needleman-Wunsch of a sequence against a POA graph
 // (spoa kNW equivalent). One engine per thread; buffers are reused.
 class NWEngine {
@@ -87,7 +98,10 @@ class NWEngine {
   NWEngine(int8_t match, int8_t mismatch, int8_t gap)
       : match_(match), mismatch_(mismatch), gap_(gap) {}
 
-  Alignment align(const char* seq, uint32_t len, const Graph& graph);
+  // stats: when given, the matrix's score range is folded into it (one more
+  // pass over the matrix; the polishing path passes none and pays nothing)
+  Alignment align(const char* seq, uint32_t len, const Graph& graph,
+                  ScoreStats* stats = nullptr);
 
  private:
   int8_t match_, mismatch_, gap_;

@@ -19,6 +19,7 @@ constexpr int32_t kAlignerBandWidthOpt = 10001;
 constexpr int32_t kAlignerAdaptiveBandOpt = 10002;
 constexpr int32_t kAlignerWideBandOpt = 10003;
 constexpr int32_t kPoaLargeGraphsOpt = 10004;
+constexpr int32_t kPoaScoreCheckOpt = 10005;
 
 struct option long_options[] = {
     {"include-unpolished", no_argument, nullptr, 'u'},
@@ -40,6 +41,7 @@ struct option long_options[] = {
     {"aligner-adaptive-band", no_argument, nullptr, kAlignerAdaptiveBandOpt},
     {"aligner-wide-band", no_argument, nullptr, kAlignerWideBandOpt},
     {"poa-large-graphs", no_argument, nullptr, kPoaLargeGraphsOpt},
+    {"poa-score-check", no_argument, nullptr, kPoaScoreCheckOpt},
     {nullptr, 0, nullptr, 0}};
 
 void help() {
@@ -114,7 +116,13 @@ void help() {
       "        --poa-large-graphs\n"
       "            give windows whose POA graph outgrows the GPU's node cap a second\n"
       "            pass on the GPU, in slabs of 4095 nodes, before the CPU engine\n"
-      "            takes them (no effect without -c)\n");
+      "            takes them (no effect without -c)\n"
+      "        --poa-score-check\n"
+      "            check the int16 score range of the GPU POA per window, on the GPU,\n"
+      "            instead of refusing score parameters by their worst case: allows\n"
+      "            -m up to 27 and any -x and negative -g; a window whose scores could\n"
+      "            leave the range goes to the CPU engine (no effect without -c, and\n"
+      "            none with -b, which keeps the worst-case guard)\n");
 }
 
 }  // namespace
@@ -155,6 +163,7 @@ int main(int argc, char** argv) {
       case kAlignerAdaptiveBandOpt: config.aligner_adaptive_band = true; break;
       case kAlignerWideBandOpt: config.aligner_wide_band = true; break;
       case kPoaLargeGraphsOpt: config.poa_large_graphs = true; break;
+      case kPoaScoreCheckOpt: config.poa_score_check = true; break;
       default: exit(1);
     }
   }

@@ -57,6 +57,11 @@ struct PolisherConfig {
   // cap: they run again in slabs of twice the capacity (4095 nodes) before
   // the CPU engine takes what is left (HIP POA batches only). Off by default.
   bool poa_large_graphs = false;
+  // replaces the class-wide int16 score guard of the HIP POA engine by a
+  // small static condition on the parameters plus a per-window check on the
+  // device (hip/poa_types.hpp, docs/DESIGN.md "Score check"); a refused window
+  // goes to the CPU engine. Does nothing with banded_poa. Off by default.
+  bool poa_score_check = false;
 };
 
 class Polisher {

@@ -96,7 +96,7 @@ std::vector<uint32_t> Window::layer_order() const {
   return order;
 }
 
-bool Window::generate_consensus(poa::NWEngine& engine, bool trim) {
+bool Window::generate_consensus(poa::NWEngine& engine, bool trim, poa::ScoreStats* stats) {
   const Layer& base = layers_.front();
   if (layers_.size() < 3) {
     // under-covered: pass the backbone through, flagged unpolished
@@ -118,11 +118,11 @@ bool Window::generate_consensus(poa::NWEngine& engine, bool trim) {
     poa::Alignment aln;
     const bool spans_window = l.begin < edge_margin && l.end > base.seq_len - edge_margin;
     if (spans_window) {
-      aln = engine.align(l.seq, l.seq_len, graph);
+      aln = engine.align(l.seq, l.seq_len, graph, stats);
     } else {
       std::vector<int32_t> node_map;
       poa::Graph ranged = graph.subgraph(l.begin, l.end, &node_map);
-      aln = engine.align(l.seq, l.seq_len, ranged);
+      aln = engine.align(l.seq, l.seq_len, ranged, stats);
       poa::Graph::update_alignment(&aln, node_map);
     }
 

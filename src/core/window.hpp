@@ -19,6 +19,7 @@ namespace rga {
 
 namespace poa {
 class NWEngine;
+struct ScoreStats;
 }
 
 enum class WindowType {
@@ -73,8 +74,9 @@ class Window {
                  uint32_t quality_length, uint32_t begin, uint32_t end);
 
   // CPU POA consensus; returns true when a real consensus was generated
-  // (false = backbone copy for under-covered windows).
-  bool generate_consensus(poa::NWEngine& engine, bool trim);
+  // (false = backbone copy for under-covered windows). stats: when given,
+  // the score range of every layer's DP matrix (poa::ScoreStats).
+  bool generate_consensus(poa::NWEngine& engine, bool trim, poa::ScoreStats* stats = nullptr);
 
   // Node count of the POA graph after the last generate_consensus() (0 when
   // no graph was built); the GPU engine's node caps are tested against it.

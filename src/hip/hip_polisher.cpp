@@ -65,22 +65,23 @@ void release_aligner(int device, uint32_t band, std::unique_ptr<hip::AlignerBatc
   p.aligner.emplace_back(key, std::move(b));
 }
 
-// depth stays below 2^14 (the device caps it at 200); a batch with a large
-// slab pool is another batch than one without
+// depth stays below 2^13 (the device caps it at 200); a batch with a large
+// slab pool is another batch than one without, and so is one that runs the
+// checked kernels
 uint64_t poa_key(int device, int8_t m, int8_t x, int8_t g, bool banded, uint32_t depth,
-                 bool large_graphs) {
+                 bool large_graphs, bool score_check) {
   return (static_cast<uint64_t>(device) << 40) |
          (static_cast<uint64_t>(static_cast<uint8_t>(m)) << 32) |
          (static_cast<uint64_t>(static_cast<uint8_t>(x)) << 24) |
          (static_cast<uint64_t>(static_cast<uint8_t>(g)) << 16) |
          (static_cast<uint64_t>(banded) << 15) | (static_cast<uint64_t>(large_graphs) << 14) |
-         depth;
+         (static_cast<uint64_t>(score_check) << 13) | depth;
 }
 
 std::unique_ptr<hip::PoaBatch> acquire_poa(int device, size_t budget, int8_t m, int8_t x,
                                            int8_t g, bool banded, uint32_t depth,
-                                           bool large_graphs) {
-  const uint64_t key = poa_key(device, m, x, g, banded, depth, large_graphs);
+                                           bool large_graphs, bool score_check) {
+  const uint64_t key = poa_key(device, m, x, g, banded, depth, large_graphs, score_check);
   auto& p = pools();
   {
     std::lock_guard<std::mutex> lock(p.mutex);
@@ -92,7 +93,8 @@ std::unique_ptr<hip::PoaBatch> acquire_poa(int device, size_t budget, int8_t m, 
       }
     }
   }
-  return std::make_unique<hip::PoaBatch>(device, budget, m, x, g, banded, depth, large_graphs);
+  return std::make_unique<hip::PoaBatch>(device, budget, m, x, g, banded, depth, large_graphs,
+                                         score_check);
 }
 
 void release_poa(uint64_t key, std::unique_ptr<hip::PoaBatch> b) {
@@ -287,9 +289,15 @@ class HipPolisher : public Polisher {
       Polisher::polish(dst, drop_unpolished);
       return;
     }
+    // with the score check the checked kernels guard every window themselves
+    // and neither worst-case guard below applies; where it does not apply
+    // (banded rows, or its static condition fails) the run is what it is
+    // without the option
+    const bool score_check = hip::PoaBatch::score_check_applies(
+        config_.match, config_.mismatch, config_.gap, config_.banded_poa, config_.poa_score_check);
     // int16 device scores bound the usable score magnitudes
     // (poa_batch.cpp guard); prefer the CPU engine over dying
-    {
+    if (!score_check) {
       const int32_t worst_param =
           std::max({std::abs(static_cast<int32_t>(config_.match)),
                     std::abs(static_cast<int32_t>(config_.mismatch)),
@@ -311,8 +319,9 @@ class HipPolisher : public Polisher {
     // the large-graph pass has a score guard of its own (its graphs are
     // twice as deep); where it fails the run goes on without the pass
     bool large_graphs = config_.poa_large_graphs;
-    if (large_graphs && !hip::PoaBatch::large_scores_fit(config_.match, config_.mismatch,
-                                                         config_.gap, config_.banded_poa)) {
+    if (large_graphs && !score_check &&
+        !hip::PoaBatch::large_scores_fit(config_.match, config_.mismatch, config_.gap,
+                                         config_.banded_poa)) {
       fprintf(stderr,
               "[rga::HipPolisher] warning: score parameters too large for the int16 "
               "scores of the large-graph pass; running without it\n");
@@ -334,9 +343,10 @@ class HipPolisher : public Polisher {
         for (uint32_t b = 0; b < config_.poa_batches; ++b) {
           batches.emplace_back(acquire_poa(d, budget, config_.match, config_.mismatch,
                                            config_.gap, config_.banded_poa, kMaxDepth,
-                                           large_graphs));
+                                           large_graphs, score_check));
           batch_keys.emplace_back(poa_key(d, config_.match, config_.mismatch, config_.gap,
-                                          config_.banded_poa, kMaxDepth, large_graphs));
+                                          config_.banded_poa, kMaxDepth, large_graphs,
+                                          score_check));
         }
       }
     } catch (const std::exception& e) {
@@ -357,6 +367,7 @@ class HipPolisher : public Polisher {
     std::mutex status_mutex;
     std::atomic<int64_t> t_fill_ns{0}, t_gpu_ns{0};
     std::atomic<uint64_t> large_completed{0};
+    std::atomic<uint64_t> score_refused{0};
 
     auto worker = [&](hip::PoaBatch* batch) {
       using clk = std::chrono::steady_clock;
@@ -406,6 +417,7 @@ class HipPolisher : public Polisher {
         }
         auto status = batch->generate(config_.trim);
         large_completed += batch->large_completed();
+        score_refused += batch->score_refused();
         t_gpu_ns += (clk::now() - t1).count();
         {
           std::lock_guard<std::mutex> lock(status_mutex);
@@ -436,6 +448,10 @@ class HipPolisher : public Polisher {
     if (large_completed.load() > 0) {
       fprintf(stderr, "[rga::HipPolisher] %lu window(s) completed by the large-graph pass\n",
               static_cast<unsigned long>(large_completed.load()));
+    }
+    if (score_refused.load() > 0) {
+      fprintf(stderr, "[rga::HipPolisher] %lu window(s) refused by the score check\n",
+              static_cast<unsigned long>(score_refused.load()));
     }
 
     // CPU fallback for every window the GPU did not polish
@@ -519,12 +535,13 @@ std::vector<std::pair<std::string, bool>> poa_windows_gpu(
     const std::vector<std::vector<std::tuple<std::string, std::string, uint32_t, uint32_t>>>&
         window_layers,
     int8_t match, int8_t mismatch, int8_t gap, bool banded, bool trim, bool tgs,
-    bool large_graphs) {
+    bool large_graphs, bool score_check) {
   std::vector<std::pair<std::string, bool>> out(window_layers.size());
   std::vector<std::shared_ptr<Window>> windows =
       windows_from_layers(window_layers, tgs, "poa_windows_gpu");
 
-  hip::PoaBatch batch(0, 4ull << 30, match, mismatch, gap, banded, 200, large_graphs);
+  hip::PoaBatch batch(0, 4ull << 30, match, mismatch, gap, banded, 200, large_graphs,
+                      score_check);
   size_t begin = 0;
   std::vector<int64_t> slot_of(windows.size(), -1);
   auto flush = [&](size_t end) {
@@ -574,10 +591,11 @@ std::vector<std::pair<std::string, bool>> poa_windows_gpu(
 // (< 3 layers, backbone too long) or that do not fit one batch.
 std::vector<std::tuple<int32_t, std::vector<uint16_t>, std::vector<std::vector<uint16_t>>>>
 poa_window_graph_gpu(const RawWindows& window_layers, int8_t match, int8_t mismatch, int8_t gap,
-                     bool banded, bool large_graphs) {
+                     bool banded, bool large_graphs, bool score_check) {
   std::vector<std::shared_ptr<Window>> windows =
       windows_from_layers(window_layers, true, "poa_window_graph_gpu");
-  hip::PoaBatch batch(0, 4ull << 30, match, mismatch, gap, banded, 200, large_graphs);
+  hip::PoaBatch batch(0, 4ull << 30, match, mismatch, gap, banded, 200, large_graphs,
+                      score_check);
   for (const auto& w : windows) {
     bool never_fits = false;
     if (w->num_layers() < 3 || !batch.add_window(w, &never_fits)) {

@@ -30,16 +30,21 @@ constexpr size_t kLargePerWindow =
 }  // namespace
 
 bool PoaBatch::large_scores_fit(int8_t match, int8_t mismatch, int8_t gap, bool banded) {
-  const int32_t worst = static_cast<int32_t>(LL.max_nodes + LL.matrix_width) *
-                        std::max({std::abs(static_cast<int32_t>(match)),
-                                  std::abs(static_cast<int32_t>(mismatch)),
-                                  std::abs(static_cast<int32_t>(gap))});
-  return worst <= (banded ? 27000 : 28000);
+  return poa_scores_fit_worst_case(LL, match, mismatch, gap, banded);
+}
+
+bool PoaBatch::score_check_applies(int8_t match, int8_t mismatch, int8_t gap, bool banded,
+                                   bool score_check) {
+  static_assert(L.matrix_width == LL.matrix_width);
+  // banded rows reuse the values below the floor as out-of-band marks, and
+  // rows whose band excludes column 0 have no column-0 score to check
+  return score_check && !banded && poa_score_check_static(match, mismatch, gap, L.matrix_width);
 }
 
 PoaBatch::PoaBatch(int device, size_t mem_budget, int8_t match, int8_t mismatch, int8_t gap,
-                   bool banded, uint32_t max_depth, bool large_graphs)
-    : device_(device), match_(match), mismatch_(mismatch), gap_(gap), max_depth_(max_depth) {
+                   bool banded, uint32_t max_depth, bool large_graphs, bool score_check)
+    : device_(device), match_(match), mismatch_(mismatch), gap_(gap), max_depth_(max_depth),
+      score_check_(score_check_applies(match, mismatch, gap, banded, score_check)) {
   // int16 score guard: worst |score| <= (max_nodes + matrix_width) * max|param|
   // (banded mode additionally reserves values below -28000 as out-of-band)
   int32_t worst = static_cast<int32_t>(L.max_nodes + L.matrix_width) *
@@ -48,8 +53,10 @@ PoaBatch::PoaBatch(int device, size_t mem_budget, int8_t match, int8_t mismatch,
                             std::abs(static_cast<int32_t>(gap))});
   // the kernel clamps stored scores at -28000 in every mode, so the usable
   // magnitude is 28000 (not the int16 32767 limit); banded mode additionally
-  // reserves values below -28000 as out-of-band sentinels
-  if (worst > (banded ? 27000 : 28000)) {
+  // reserves values below -28000 as out-of-band sentinels.
+  // With the score check the checked kernels guard each window themselves,
+  // in both capacity classes, and neither product applies.
+  if (!score_check_ && worst > (banded ? 27000 : 28000)) {
     char msg[160];
     snprintf(msg, sizeof(msg),
              "[rga::hip::PoaBatch] score parameters too large for int16 GPU "
@@ -58,7 +65,7 @@ PoaBatch::PoaBatch(int device, size_t mem_budget, int8_t match, int8_t mismatch,
     throw std::runtime_error(msg);
   }
 
-  if (large_graphs && !large_scores_fit(match, mismatch, gap, banded)) {
+  if (large_graphs && !score_check_ && !large_scores_fit(match, mismatch, gap, banded)) {
     fprintf(stderr,
             "[rga::hip::PoaBatch] warning: score parameters too large for the int16 scores "
             "of the large-graph pass ((%u+%u)*max > %d); the pass is off for this batch\n",
@@ -439,7 +446,11 @@ std::vector<bool> PoaBatch::generate(bool trim) {
     const PoaVariant v = variant_of[perm[begin]];
     for (end = begin + 1; end < nw0 && variant_of[perm[end]] == v; ++end) {
     }
-    launch_poa_kernel(arena_, begin, end - begin, v, stream_);
+    if (score_check_) {
+      launch_poa_kernel_checked(arena_, begin, end - begin, v, stream_);
+    } else {
+      launch_poa_kernel(arena_, begin, end - begin, v, stream_);
+    }
   }
 
   const size_t nw = windows_.size();
@@ -493,9 +504,13 @@ std::vector<bool> PoaBatch::generate(bool trim) {
 
   // CPU-parity post-processing (reference cudabatch.cpp:199-261).
   // Kernel slot i handled original window perm[i].
+  score_refused_ = 0;
   for (size_t i = 0; i < nw; ++i) {
     const uint32_t orig = perm[i];
     auto& window = windows_[orig];
+    if (h_status_[i] == kPoaScoreRange) {
+      ++score_refused_;  // either pass; counted for the polisher's report
+    }
     if (h_status_[i] != kPoaOk || h_consensus_len_[i] == 0) {
       polished[orig] = false;  // device-side failure -> CPU fallback
       continue;
@@ -590,7 +605,11 @@ uint32_t PoaBatch::run_large_pass() {
                                  n * sizeof(PoaWindowDesc), hipMemcpyHostToDevice, s));
     RGA_HIP_CHECK(hipMemcpyAsync(const_cast<uint32_t*>(large_arena_.layer_ends_index),
                                  h_large_layer_index_, n * 4, hipMemcpyHostToDevice, s));
-    launch_poa_kernel_large(large_arena_, 0, n, stream_);
+    if (score_check_) {
+      launch_poa_kernel_large_checked(large_arena_, 0, n, stream_);
+    } else {
+      launch_poa_kernel_large(large_arena_, 0, n, stream_);
+    }
     RGA_HIP_CHECK(hipMemcpyAsync(h_large_consensus_, large_arena_.consensus,
                                  static_cast<size_t>(n) * LL.max_consensus,
                                  hipMemcpyDeviceToHost, s));
@@ -697,6 +716,7 @@ void PoaBatch::reset() {
   large_slab_of_.clear();
   large_nodes_of_.clear();
   large_completed_ = 0;
+  score_refused_ = 0;
   windows_.clear();
   seqs_added_.clear();
   pending_orders_.clear();

@@ -21,8 +21,14 @@ class PoaBatch {
   // the budget and give the windows that end with kPoaNodeOverflow a second
   // pass in them (docs/DESIGN.md, "Large-graph pass"). Off, the batch is what
   // it was without the option: no pool, the same slab count.
+  // score_check: guard the int16 scores with the static condition
+  // poa_score_check_static plus the per-row check of the checked kernels, a
+  // refused window ending with kPoaScoreRange, in place of the worst-case
+  // products below (docs/DESIGN.md, "Score check"). With banded rows, or
+  // where the static condition fails, the batch is what it is without it.
   PoaBatch(int device, size_t mem_budget, int8_t match, int8_t mismatch, int8_t gap,
-           bool banded, uint32_t max_depth, bool large_graphs = false);
+           bool banded, uint32_t max_depth, bool large_graphs = false,
+           bool score_check = false);
   ~PoaBatch();
 
   PoaBatch(const PoaBatch&) = delete;
@@ -50,6 +56,13 @@ class PoaBatch {
   uint32_t large_capacity() const { return large_slabs_; }
   // windows of the last generate() that the large-graph pass completed
   uint32_t large_completed() const { return large_completed_; }
+
+  // whether a batch built with these arguments runs the checked kernels
+  static bool score_check_applies(int8_t match, int8_t mismatch, int8_t gap, bool banded,
+                                  bool score_check);
+  bool score_checked() const { return score_check_; }
+  // windows of the last generate() that ended with kPoaScoreRange
+  uint32_t score_refused() const { return score_refused_; }
 
   // Runs the kernel and writes consensus into the windows; returns per-window
   // polish status (false = needs CPU fallback or <3-layer backbone copy).
@@ -89,6 +102,8 @@ class PoaBatch {
   size_t seq_arena_cap_;
   int8_t match_, mismatch_, gap_;
   uint32_t max_depth_;
+  bool score_check_ = false;  // the checked kernels run, both passes
+  uint32_t score_refused_ = 0;
 
   // pinned host staging
   uint8_t* h_seq_ = nullptr;

@@ -35,6 +35,7 @@
 // GPU goldens; so do we — topological order here is Kahn FIFO, not spoa DFS).
 #include <hip/hip_runtime.h>
 
+#include <cstdio>
 #include <cstdlib>
 
 #include "hip/poa_types.hpp"
@@ -56,6 +57,17 @@ constexpr bool kLarge = true;
 #else
 constexpr bool kLarge = false;
 #endif
+// The per-row score check (poa_types.hpp, poa_score_row_refused) is a template
+// flag of the kernel, CHECKED next to TIMED. The checked instantiations live
+// in translation units of their own (poa_kernel_checked.hip and
+// poa_kernel_large_checked.hip define RGA_POA_SCORE_CHECK and include this
+// file), so that the unchecked ones compile as they did before the check
+// existed and the four units build side by side.
+#ifdef RGA_POA_SCORE_CHECK
+constexpr bool kChecked = true;
+#else
+constexpr bool kChecked = false;
+#endif
 constexpr PoaLimits kL = poa_limits(kLarge);
 constexpr uint32_t kMaxW = kL.matrix_width;   // DP row width (slab and widest ring)
 constexpr uint32_t kMaxN = kL.max_nodes + 1;  // widest LDS Kahn arrays
@@ -66,7 +78,14 @@ constexpr uint32_t kMaxPre = 5;   // predecessor rows carried by the row descrip
 // Minus infinity of a multi-predecessor row, whose candidates are compared as
 // (score << 6 | edge priority) keys: far below every real score (|score| <
 // 2^18 before the clamp) and still clear of overflow after the shift.
+// The scaled scores stay above it under either guard. A predecessor value is
+// a stored one, so at least kPoaScoreFloor and, by either guard, at most
+// 28000 in magnitude; a candidate adds one score parameter, an int8, to it:
+// (28000 + 127) * 64 = 1800128 < 2^21 = 2097152. With the score check
+// (CHECKED) a parameter may reach 127 where the worst-case guard stopped at 9,
+// and the bound is the same one.
 constexpr int32_t kNegInfKeyed = -(1 << 21);
+static_assert((-kPoaScoreFloor + 127) * 64 < -kNegInfKeyed);
 
 // move byte encoding
 constexpr uint8_t kMvDiag = 0;
@@ -839,10 +858,18 @@ __device__ __forceinline__ void gather_row(const Row& row, uint32_t cbase, uint3
 // best_row), which stays wave-uniform. The context comes BY VALUE: the row
 // only reads it, and taken by reference the whole struct stayed in scratch
 // memory (208 B/lane on every variant).
-template <uint32_t WB, uint32_t MAXW, class SH>
+//
+// CHECKED: the row also applies the score check to its column-0 score
+// (poa_score_row_refused) and sets score_low, which is sticky and
+// wave-uniform, when it is refused. The row is computed all the same, with
+// clamped and possibly wrapped scores that only ever become move bytes: the
+// kernel drops the layer, and the window, after its last row. Checked kernels
+// run unbanded rows only, so every row computes h0.
+template <bool CHECKED, uint32_t WB, uint32_t MAXW, class SH>
 __device__ __forceinline__ void dp_row(const WindowCtx c, SH& s, const LayerDp& d, uint32_t r,
                                        uint64_t rd, uint64_t rd2_lanes, int lane,
-                                       int32_t& best_score, uint32_t& best_row) {
+                                       int32_t& best_score, uint32_t& best_row,
+                                       uint32_t& score_low) {
   // Every lane read the same two LDS words, so they are wave-uniform, but
   // they arrive in vector registers. The second word (rows of in-edges 1..4,
   // see pred_row_of) is only ever shifted by the wave-uniform edge index:
@@ -929,6 +956,11 @@ __device__ __forceinline__ void dp_row(const WindowCtx c, SH& s, const LayerDp& 
       }
     }
     h0 = best0 + c.g;
+    if constexpr (CHECKED) {
+      // every lane holds the same h0: take it to a scalar register, so that
+      // the compare and the flag cost the row no vector register
+      score_low |= poa_score_row_refused(__builtin_amdgcn_readfirstlane(h0), len, c.g) ? 1u : 0u;
+    }
     if (lane == 0) {
       if (store_row) {
         Hrow[0] = static_cast<int16_t>(h0);
@@ -1130,7 +1162,7 @@ __device__ __forceinline__ void dp_row(const WindowCtx c, SH& s, const LayerDp& 
     for (uint32_t w = 0; w < WB; ++w) {
       const uint32_t j = cbase + 1 + w;
       const int32_t h = max(us[w], excl) + static_cast<int32_t>(j) * c.g;
-      harr[w] = h < -28000 ? -28000 : h;
+      harr[w] = h < kPoaScoreFloor ? kPoaScoreFloor : h;
       const uint32_t mv =
           (h != v[w]) ? kMvLeft : static_cast<uint32_t>(mvbase >> (8 * w)) & 0xffu;
       if (WB == 8) {
@@ -1395,7 +1427,9 @@ __device__ __attribute__((noinline)) int32_t traceback_d(const TracebackArrays c
 // (waves/SIMD floor): the 8-wide variants otherwise help themselves to the
 // full 128-VGPR budget of 4 waves/SIMD and registers — not LDS — become
 // the residency limiter.
-template <bool TIMED, uint32_t WB, uint32_t MAXW, uint32_t MAXN, uint32_t MINWAVES>
+// CHECKED compiles the per-row score check in (dp_row): a window one of whose
+// rows is refused ends with kPoaScoreRange.
+template <bool TIMED, bool CHECKED, uint32_t WB, uint32_t MAXW, uint32_t MAXN, uint32_t MINWAVES>
 __launch_bounds__(kLanes, MINWAVES)
 __global__ void poa_window_kernel(PoaDeviceArena a, uint32_t window_base,
                                   uint32_t num_windows) {
@@ -1471,13 +1505,16 @@ __global__ void poa_window_kernel(PoaDeviceArena a, uint32_t window_base,
     d.rlo = d.sub ? c.rank[span_word >> 16] : 0;
     d.rhi = d.sub ? c.rank[span_word & 0xffffu] : n - 1;
     d.bw = a.band_width;
-    d.banded = (d.bw != 0) && (d.bw < len);
+    // (the checked kernels are launched with band_width 0 only, and say so at
+    // compile time: their rows carry no band code)
+    d.banded = !CHECKED && (d.bw != 0) && (d.bw < len);
     d.slope16 = d.banded ? static_cast<uint32_t>((static_cast<uint64_t>(len) << 16) /
                                                  (d.rhi - d.rlo + 1))
                          : 0;
 
     int32_t best_score = kNegInf;
     uint32_t best_row = 0;
+    uint32_t score_low = 0;  // CHECKED: a row of this layer was refused
     (void)lap();
 
     // Row descriptors are staged 64 at a time through LDS with one
@@ -1492,8 +1529,9 @@ __global__ void poa_window_kernel(PoaDeviceArena a, uint32_t window_base,
       wave_lds_sync();
       const uint32_t rlim = min(d.rhi + 1, rblk + kLanes);
       for (uint32_t r = max(rblk, d.rlo); r < rlim; ++r) {
-        dp_row<WB, MAXW>(c, s, d, r, s.u.dp.rd_block[r - rblk], s.u.dp.rd2_block[r - rblk], lane,
-                         best_score, best_row);
+        dp_row<CHECKED, WB, MAXW>(c, s, d, r, s.u.dp.rd_block[r - rblk],
+                                  s.u.dp.rd2_block[r - rblk], lane, best_score, best_row,
+                                  score_low);
       }
       wave_lds_sync();  // rows done before the next cooperative rd_block load
     }
@@ -1509,13 +1547,23 @@ __global__ void poa_window_kernel(PoaDeviceArena a, uint32_t window_base,
     int lane_g = lane;
     asm volatile("" : "+v"(lane_g));
 
+    // A layer that tripped the score check stops here: its moves come from
+    // clamped scores, so nothing of it may reach the graph. The status is
+    // wave-uniform and final; every phase below and the layer loop are gated
+    // by it.
+    if (CHECKED && score_low != 0) {
+      c.status = kPoaScoreRange;
+    }
+
     // ---- traceback, all lanes (the ring is dead: its LDS is reused) ----
-    c.status = traceback_d({(RGA_GLOBAL const uint8_t*)c.moves,
-                            (RGA_GLOBAL const uint64_t*)c.row_desc,
-                            (RGA_GLOBAL const uint16_t*)c.rank,
-                            (RGA_GLOBAL const uint16_t*)c.in_edges,
-                            (RGA_GLOBAL int32_t*)c.aln_nodes},
-                           (LdsU16*)s.u.tb.pred0, d.rlo, best_row, len, lane_g);
+    if (!CHECKED || c.status == kPoaOk) {
+      c.status = traceback_d({(RGA_GLOBAL const uint8_t*)c.moves,
+                              (RGA_GLOBAL const uint64_t*)c.row_desc,
+                              (RGA_GLOBAL const uint16_t*)c.rank,
+                              (RGA_GLOBAL const uint16_t*)c.in_edges,
+                              (RGA_GLOBAL int32_t*)c.aln_nodes},
+                             (LdsU16*)s.u.tb.pred0, d.rlo, best_row, len, lane_g);
+    }
     __syncthreads();  // the path -> visible to the whole wave
     t_tb += lap();
 
@@ -1582,21 +1630,29 @@ __global__ void poa_window_kernel(PoaDeviceArena a, uint32_t window_base,
 // window) beats a 9-wide single-pass variant by ~8% — non-power-of-two
 // unrolls lose more in generated address code than the extra, mostly
 // empty pass costs. The ring width (LDS) sets occupancy; see Shared<W>.
+// A unit's launch function is named for its class and for the score check.
+#ifdef RGA_POA_SCORE_CHECK
+#define RGA_POA_LAUNCH(name) name##_checked
+#else
+#define RGA_POA_LAUNCH(name) name
+#endif
+
 #ifdef RGA_POA_LARGE_CLASS
 // the large class has the one variant
 template <bool TIMED>
 void launch_large(const PoaDeviceArena& arena, uint32_t window_base, uint32_t num_windows,
                   hipStream_t stream) {
   constexpr PoaVariantParams p = kPoaLargeVariant;
-  hipLaunchKernelGGL(
-      (poa_window_kernel<TIMED, p.cols_per_lane, p.ring_width, p.node_cap, p.min_waves>),
-      dim3(num_windows), dim3(kLanes), 0, stream, arena, window_base, num_windows);
+  hipLaunchKernelGGL((poa_window_kernel<TIMED, kChecked, p.cols_per_lane, p.ring_width,
+                                        p.node_cap, p.min_waves>),
+                     dim3(num_windows), dim3(kLanes), 0, stream, arena, window_base,
+                     num_windows);
 }
 
 }  // namespace
 
-void launch_poa_kernel_large(const PoaDeviceArena& arena, uint32_t window_base,
-                             uint32_t num_windows, void* stream) {
+void RGA_POA_LAUNCH(launch_poa_kernel_large)(const PoaDeviceArena& arena, uint32_t window_base,
+                                             uint32_t num_windows, void* stream) {
   static const bool timed = getenv("RGA_POA_TIMING") != nullptr;
   auto st = static_cast<hipStream_t>(stream);
   if (timed) {
@@ -1610,9 +1666,10 @@ template <bool TIMED, PoaVariant V>
 void launch_variant(const PoaDeviceArena& arena, uint32_t window_base, uint32_t num_windows,
                     hipStream_t stream) {
   constexpr PoaVariantParams p = kPoaVariants[V];
-  hipLaunchKernelGGL(
-      (poa_window_kernel<TIMED, p.cols_per_lane, p.ring_width, p.node_cap, p.min_waves>),
-      dim3(num_windows), dim3(kLanes), 0, stream, arena, window_base, num_windows);
+  hipLaunchKernelGGL((poa_window_kernel<TIMED, kChecked, p.cols_per_lane, p.ring_width,
+                                        p.node_cap, p.min_waves>),
+                     dim3(num_windows), dim3(kLanes), 0, stream, arena, window_base,
+                     num_windows);
 }
 
 template <bool TIMED>
@@ -1626,18 +1683,28 @@ void dispatch_variant(const PoaDeviceArena& arena, uint32_t window_base, uint32_
     case kPoaFull:
       return launch_variant<TIMED, kPoaFull>(arena, window_base, num_windows, stream);
     case kPoaBandedMid:
-      return launch_variant<TIMED, kPoaBandedMid>(arena, window_base, num_windows, stream);
     case kPoaBandedFull:
-      return launch_variant<TIMED, kPoaBandedFull>(arena, window_base, num_windows, stream);
+      // the checked unit has no banded instantiations: banded rows reuse the
+      // values below the floor, and the host keeps the check off with -b
+      if constexpr (!kChecked) {
+        if (variant == kPoaBandedMid) {
+          return launch_variant<TIMED, kPoaBandedMid>(arena, window_base, num_windows, stream);
+        }
+        return launch_variant<TIMED, kPoaBandedFull>(arena, window_base, num_windows, stream);
+      }
+      break;
     case kPoaNumVariants:
       break;
   }
+  fprintf(stderr, "[rga::hip::launch_poa_kernel] error: no kernel for variant %u\n",
+          static_cast<unsigned>(variant));
+  abort();
 }
 
 }  // namespace
 
-void launch_poa_kernel(const PoaDeviceArena& arena, uint32_t window_base,
-                       uint32_t num_windows, PoaVariant variant, void* stream) {
+void RGA_POA_LAUNCH(launch_poa_kernel)(const PoaDeviceArena& arena, uint32_t window_base,
+                                       uint32_t num_windows, PoaVariant variant, void* stream) {
   static const bool timed = getenv("RGA_POA_TIMING") != nullptr;
   auto st = static_cast<hipStream_t>(stream);
   if (timed) {

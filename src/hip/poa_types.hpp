@@ -51,7 +51,53 @@ enum PoaStatus : int32_t {
   kPoaConsensusOverflow = 4,
   kPoaNotRun = 5,
   kPoaWidthOverflow = 6,  // layer wider than the launched ring variant
+  kPoaScoreRange = 7,     // refused by the per-window score check (below)
 };
+
+// ---- int16 score range ----
+// DP scores are stored as int16 and clamped at kPoaScoreFloor from below.
+// Without the score check (PoaBatch, score_check off) a batch is guarded by
+// one worst-case product per capacity class, poa_scores_fit_worst_case. With
+// it the guard is a small static condition on the parameters
+// (poa_score_check_static) plus one compare per DP row on the device
+// (poa_score_row_refused); docs/DESIGN.md, "Score check". The host, the
+// kernel and the CPU model (NWEngine's ScoreStats) all take the rule from
+// here.
+inline constexpr int32_t kPoaScoreFloor = -28000;
+inline constexpr int32_t kPoaScoreFloorBanded = -27000;  // banded rows mark out-of-band
+                                                         // cells with values below the floor
+
+constexpr int32_t poa_abs(int32_t v) { return v < 0 ? -v : v; }
+constexpr int32_t poa_max(int32_t a, int32_t b) { return a > b ? a : b; }
+
+// the class-wide guard: (max_nodes + matrix_width) * max(|m|,|x|,|g|) within
+// the floor
+constexpr bool poa_scores_fit_worst_case(const PoaLimits& l, int32_t m, int32_t x, int32_t g,
+                                         bool banded) {
+  const int32_t worst = static_cast<int32_t>(l.max_nodes + l.matrix_width) *
+                        poa_max(poa_abs(m), poa_max(poa_abs(x), poa_abs(g)));
+  return worst <= -(banded ? kPoaScoreFloorBanded : kPoaScoreFloor);
+}
+
+// Static part of the score check. Gaps cost something, so that a run of
+// horizontal gaps from column 0 bounds every cell of a row from below; and no
+// score exceeds the layer length (at most matrix_width - 1 columns) times the
+// best per-column gain.
+constexpr bool poa_score_check_static(int32_t m, int32_t x, int32_t g, uint32_t matrix_width) {
+  return g < 0 && poa_max(poa_max(m, x), 0) * static_cast<int32_t>(matrix_width - 1) <=
+                      -kPoaScoreFloor;
+}
+
+// Per-row part: h0 is the row's column-0 score, len the layer's length. No
+// cell of the row is below h0 + len * g, so a row that passes stores no
+// clamped score. Conservative: a refused row need not hold a cell that low.
+constexpr bool poa_score_row_refused(int32_t h0, uint32_t len, int32_t g) {
+  return h0 + static_cast<int32_t>(len) * g < kPoaScoreFloor;
+}
+static_assert(poa_score_check_static(27, -20, -13, 1024) &&
+              !poa_score_check_static(28, -20, -13, 1024) &&
+              !poa_score_check_static(3, -5, 0, 1024));
+static_assert(!poa_score_row_refused(-14000, 500, -28) && poa_score_row_refused(-14500, 500, -29));
 
 // ---- kernel variants ----
 // The kernel is instantiated once per row of kPoaVariants (times timed /
@@ -262,5 +308,14 @@ void launch_poa_kernel(const PoaDeviceArena& arena, uint32_t window_base,
 // the one variant kPoaLargeVariant.
 void launch_poa_kernel_large(const PoaDeviceArena& arena, uint32_t window_base,
                              uint32_t num_windows, void* stream);
+
+// The same two with the per-row score check compiled in (poa_kernel_checked.hip,
+// poa_kernel_large_checked.hip): a window that trips it ends with
+// kPoaScoreRange. Unbanded rows only: arena.band_width must be 0, so the
+// variant is never one of the banded ones.
+void launch_poa_kernel_checked(const PoaDeviceArena& arena, uint32_t window_base,
+                               uint32_t num_windows, PoaVariant variant, void* stream);
+void launch_poa_kernel_large_checked(const PoaDeviceArena& arena, uint32_t window_base,
+                                     uint32_t num_windows, void* stream);
 
 }  // namespace rga::hip

@@ -39,12 +39,12 @@ std::vector<std::pair<std::string, bool>> poa_windows_gpu(
     const std::vector<std::vector<std::tuple<std::string, std::string, uint32_t, uint32_t>>>&
         window_layers,
     int8_t match, int8_t mismatch, int8_t gap, bool banded, bool trim, bool tgs,
-    bool large_graphs);
+    bool large_graphs, bool score_check);
 std::vector<std::tuple<int32_t, std::vector<uint16_t>, std::vector<std::vector<uint16_t>>>>
 poa_window_graph_gpu(
     const std::vector<std::vector<std::tuple<std::string, std::string, uint32_t, uint32_t>>>&
         window_layers,
-    int8_t match, int8_t mismatch, int8_t gap, bool banded, bool large_graphs);
+    int8_t match, int8_t mismatch, int8_t gap, bool banded, bool large_graphs, bool score_check);
 }
 
 namespace py = pybind11;
@@ -57,7 +57,7 @@ std::vector<std::pair<std::string, std::string>> polish(
     double quality_threshold, double error_threshold, bool trim, int8_t match, int8_t mismatch,
     int8_t gap, uint32_t threads, uint32_t poa_batches, bool banded_poa, uint32_t aligner_batches,
     uint32_t aligner_band_width, bool include_unpolished, bool aligner_adaptive_band,
-    bool aligner_wide_band, bool poa_large_graphs) {
+    bool aligner_wide_band, bool poa_large_graphs, bool poa_score_check) {
   rga::PolisherConfig config;
   config.type = fragment_correction ? rga::PolisherType::kF : rga::PolisherType::kC;
   config.window_length = window_length;
@@ -75,6 +75,7 @@ std::vector<std::pair<std::string, std::string>> polish(
   config.aligner_adaptive_band = aligner_adaptive_band;
   config.aligner_wide_band = aligner_wide_band;
   config.poa_large_graphs = poa_large_graphs;
+  config.poa_score_check = poa_score_check;
 
   std::vector<std::pair<std::string, std::string>> result;
   {
@@ -238,6 +239,41 @@ std::vector<uint32_t> poa_window_node_counts(
   return out;
 }
 
+// CPU-only: the score range of each window's DP matrices in the CPU engine,
+// (check_min, true_min, true_max) of poa::ScoreStats over all layers;
+// the model of the device's per-window score check. Windows that build no
+// graph are refused.
+std::vector<std::tuple<int64_t, int64_t, int64_t>> poa_window_score_bounds(
+    const std::vector<std::vector<std::tuple<std::string, std::string, uint32_t, uint32_t>>>&
+        window_layers,
+    int8_t match, int8_t mismatch, int8_t gap) {
+  py::gil_scoped_release release;
+  rga::poa::NWEngine engine(match, mismatch, gap);
+  std::vector<std::tuple<int64_t, int64_t, int64_t>> out;
+  out.reserve(window_layers.size());
+  for (const auto& layers : window_layers) {
+    if (layers.size() < 3) {
+      throw std::runtime_error("poa_window_score_bounds: a window needs a backbone and two layers");
+    }
+    const auto& bb = layers.front();
+    auto w = rga::createWindow(0, 0, rga::WindowType::kTGS, std::get<0>(bb).data(),
+                               static_cast<uint32_t>(std::get<0>(bb).size()),
+                               std::get<1>(bb).data(),
+                               static_cast<uint32_t>(std::get<1>(bb).size()));
+    for (size_t i = 1; i < layers.size(); ++i) {
+      const auto& l = layers[i];
+      const std::string& q = std::get<1>(l);
+      w->add_layer(std::get<0>(l).data(), static_cast<uint32_t>(std::get<0>(l).size()),
+                   q.empty() ? nullptr : q.data(), static_cast<uint32_t>(q.size()),
+                   std::get<2>(l), std::get<3>(l));
+    }
+    rga::poa::ScoreStats stats;
+    w->generate_consensus(engine, false, &stats);
+    out.emplace_back(stats.check_min, stats.true_min, stats.true_max);
+  }
+  return out;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(_racon, m) {
@@ -251,7 +287,7 @@ PYBIND11_MODULE(_racon, m) {
         py::arg("banded_poa") = false, py::arg("aligner_batches") = 0,
         py::arg("aligner_band_width") = 0, py::arg("include_unpolished") = false,
         py::arg("aligner_adaptive_band") = false, py::arg("aligner_wide_band") = false,
-        py::arg("poa_large_graphs") = false,
+        py::arg("poa_large_graphs") = false, py::arg("poa_score_check") = false,
         "Polish targets with reads+overlaps; returns [(name, sequence)].");
 
   m.def("device_count", [] { return rga::hip::runtime_device_count(); },
@@ -340,30 +376,41 @@ PYBIND11_MODULE(_racon, m) {
   m.def("poa_windows_cpu", &poa_windows_cpu, py::arg("windows"), py::arg("match") = 3,
         py::arg("mismatch") = -5, py::arg("gap") = -4, py::arg("trim") = true,
         py::arg("tgs") = true);
+  m.def("poa_window_score_bounds", &poa_window_score_bounds, py::arg("windows"),
+        py::arg("match") = 3, py::arg("mismatch") = -5, py::arg("gap") = -4,
+        "CPU model of the HIP POA engine's score check: per window (check_min, true_min, "
+        "true_max) over the DP matrices of all its layers in the CPU engine. check_min is the "
+        "smallest H[row][0] + len * gap, which the device compares with -28000; true_min and "
+        "true_max are the smallest and largest cells.");
   m.def("poa_window_node_counts", &poa_window_node_counts, py::arg("windows"),
         py::arg("match") = 3, py::arg("mismatch") = -5, py::arg("gap") = -4);
   m.def("poa_windows_gpu", [](const std::vector<std::vector<
                                   std::tuple<std::string, std::string, uint32_t, uint32_t>>>& w,
                               int8_t match, int8_t mismatch, int8_t gap, bool banded,
-                              bool trim, bool tgs, bool large_graphs) {
+                              bool trim, bool tgs, bool large_graphs, bool score_check) {
     py::gil_scoped_release release;
-    return rga::hip::poa_windows_gpu(w, match, mismatch, gap, banded, trim, tgs, large_graphs);
+    return rga::hip::poa_windows_gpu(w, match, mismatch, gap, banded, trim, tgs, large_graphs,
+                                     score_check);
   }, py::arg("windows"), py::arg("match") = 3, py::arg("mismatch") = -5,
      py::arg("gap") = -4, py::arg("banded") = false, py::arg("trim") = true,
-     py::arg("tgs") = true, py::arg("large_graphs") = false);
+     py::arg("tgs") = true, py::arg("large_graphs") = false, py::arg("score_check") = false);
   m.def("poa_window_graph_gpu",
         [](const std::vector<
                std::vector<std::tuple<std::string, std::string, uint32_t, uint32_t>>>& w,
-           int8_t match, int8_t mismatch, int8_t gap, bool banded, bool large_graphs) {
+           int8_t match, int8_t mismatch, int8_t gap, bool banded, bool large_graphs,
+           bool score_check) {
           py::gil_scoped_release release;
-          return rga::hip::poa_window_graph_gpu(w, match, mismatch, gap, banded, large_graphs);
+          return rga::hip::poa_window_graph_gpu(w, match, mismatch, gap, banded, large_graphs,
+                                                score_check);
         },
         py::arg("windows"), py::arg("match") = 3, py::arg("mismatch") = -5, py::arg("gap") = -4,
         py::arg("banded") = false, py::arg("large_graphs") = false,
+        py::arg("score_check") = false,
         "Test entry: the windows through the GPU POA kernel in one batch, then per window "
         "(status, rank per node, out-edge targets per node) read back from its slab; the "
         "lists are empty unless status is 0. large_graphs: with the large-graph pass, whose "
-        "windows are read back from their large slabs.");
+        "windows are read back from their large slabs. score_check: with the per-window "
+        "score check; a refused window has status 7.");
   m.def("poa_consensus", &poa_consensus, py::arg("sequences"),
         py::arg("qualities") = std::vector<std::string>(), py::arg("match") = 5,
         py::arg("mismatch") = -4, py::arg("gap") = -8);
