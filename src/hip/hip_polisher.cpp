@@ -535,13 +535,14 @@ std::vector<std::pair<std::string, bool>> poa_windows_gpu(
     const std::vector<std::vector<std::tuple<std::string, std::string, uint32_t, uint32_t>>>&
         window_layers,
     int8_t match, int8_t mismatch, int8_t gap, bool banded, bool trim, bool tgs,
-    bool large_graphs, bool score_check) {
+    bool large_graphs, bool score_check, bool lean_rows) {
   std::vector<std::pair<std::string, bool>> out(window_layers.size());
   std::vector<std::shared_ptr<Window>> windows =
       windows_from_layers(window_layers, tgs, "poa_windows_gpu");
 
   hip::PoaBatch batch(0, 4ull << 30, match, mismatch, gap, banded, 200, large_graphs,
                       score_check);
+  batch.set_lean_rows(lean_rows);
   size_t begin = 0;
   std::vector<int64_t> slot_of(windows.size(), -1);
   auto flush = [&](size_t end) {
@@ -553,6 +554,7 @@ std::vector<std::pair<std::string, bool>> poa_windows_gpu(
       }
     }
     batch.reset();
+    batch.set_lean_rows(lean_rows);  // reset() puts the default back
     begin = end;
   };
   size_t next_slot = 0;
@@ -591,11 +593,12 @@ std::vector<std::pair<std::string, bool>> poa_windows_gpu(
 // (< 3 layers, backbone too long) or that do not fit one batch.
 std::vector<std::tuple<int32_t, std::vector<uint16_t>, std::vector<std::vector<uint16_t>>>>
 poa_window_graph_gpu(const RawWindows& window_layers, int8_t match, int8_t mismatch, int8_t gap,
-                     bool banded, bool large_graphs, bool score_check) {
+                     bool banded, bool large_graphs, bool score_check, bool lean_rows) {
   std::vector<std::shared_ptr<Window>> windows =
       windows_from_layers(window_layers, true, "poa_window_graph_gpu");
   hip::PoaBatch batch(0, 4ull << 30, match, mismatch, gap, banded, 200, large_graphs,
                       score_check);
+  batch.set_lean_rows(lean_rows);
   for (const auto& w : windows) {
     bool never_fits = false;
     if (w->num_layers() < 3 || !batch.add_window(w, &never_fits)) {

@@ -43,14 +43,14 @@ void runtime_device_synchronize() {}
 void release_batch_pools() {}
 std::vector<std::pair<std::string, bool>> poa_windows_gpu(
     const std::vector<std::vector<std::tuple<std::string, std::string, uint32_t, uint32_t>>>&,
-    int8_t, int8_t, int8_t, bool, bool, bool, bool, bool) {
+    int8_t, int8_t, int8_t, bool, bool, bool, bool, bool, bool) {
   fprintf(stderr, "[rga::hip::poa_windows_gpu] error: no HIP backend in this build!\n");
   exit(1);
 }
 std::vector<std::tuple<int32_t, std::vector<uint16_t>, std::vector<std::vector<uint16_t>>>>
 poa_window_graph_gpu(
     const std::vector<std::vector<std::tuple<std::string, std::string, uint32_t, uint32_t>>>&,
-    int8_t, int8_t, int8_t, bool, bool, bool) {
+    int8_t, int8_t, int8_t, bool, bool, bool, bool) {
   fprintf(stderr, "[rga::hip::poa_window_graph_gpu] error: no HIP backend in this build!\n");
   exit(1);
 }

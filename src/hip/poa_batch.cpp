@@ -187,6 +187,7 @@ void PoaBatch::allocate_arenas(bool banded) {
   arena_.match = match_;
   arena_.mismatch = mismatch_;
   arena_.gap = gap_;
+  arena_.lean_rows = 0;  // set per run (generate); the large class has no lean row
   arena_.band_width = banded ? 256 : 0;  // reference static band 256
 
   if (large_slabs_ != 0) {
@@ -441,6 +442,16 @@ std::vector<bool> PoaBatch::generate(bool trim) {
   d(arena_.layer_ends_index, h_layer_index_, windows_.size() * 4);
   d(arena_.windows, h_desc_, windows_.size() * sizeof(PoaWindowDesc));
 
+  // Lean rows: the batch's switch, the range condition of the packed row
+  // (decided here, once per launch, next to the constructor's guards) and the
+  // process-wide A/B switch.
+  static const bool lean_env = [] {
+    const char* e = getenv("RGA_POA_LEAN_ROWS");
+    return e == nullptr || atoi(e) != 0;
+  }();
+  arena_.lean_rows =
+      lean_rows_ && lean_env && poa_lean_rows_fit(match_, mismatch_, gap_) ? 1 : 0;
+
   // one launch per variant over its contiguous range
   for (uint32_t begin = 0, end; begin < nw0; begin = end) {
     const PoaVariant v = variant_of[perm[begin]];
@@ -489,16 +500,23 @@ std::vector<bool> PoaBatch::generate(bool trim) {
                             hipMemcpyDeviceToHost));
     unsigned long long sum[kSlots] = {0};
     std::vector<unsigned long long> totals(nw);
+    unsigned long long rows = 0, lean = 0;
     for (size_t i = 0; i < nw; ++i) {
-      for (size_t k = 0; k < kSlots; ++k) sum[k] += t[i * kSlots + k];
+      for (size_t k = 0; k < kSlots - 1; ++k) sum[k] += t[i * kSlots + k];
+      // slot 7 holds three counts (poa_pack_counts)
+      sum[7] += poa_count_layers(t[i * kSlots + 7]);
+      lean += poa_count_lean_rows(t[i * kSlots + 7]);
+      rows += poa_count_rows(t[i * kSlots + 7]);
       totals[i] = t[i * kSlots + 6];
     }
     std::sort(totals.begin(), totals.end());
     fprintf(stderr,
             "[rga::hip::PoaBatch] timing (wall ticks, %zu windows): dp=%llu tb=%llu "
-            "add=%llu topo=%llu rdesc=%llu cons=%llu total=%llu layers=%llu\n"
+            "add=%llu topo=%llu rdesc=%llu cons=%llu total=%llu layers=%llu rows=%llu "
+            "lean_rows=%llu (%.1f%%)\n"
             "[rga::hip::PoaBatch] window total ticks: p50=%llu p90=%llu p99=%llu max=%llu\n",
-            nw, sum[0], sum[1], sum[2], sum[3], sum[4], sum[5], sum[6], sum[7],
+            nw, sum[0], sum[1], sum[2], sum[3], sum[4], sum[5], sum[6], sum[7], rows, lean,
+            rows != 0 ? 100.0 * static_cast<double>(lean) / static_cast<double>(rows) : 0.0,
             totals[nw / 2], totals[nw * 9 / 10], totals[nw * 99 / 100], totals[nw - 1]);
   }
 
@@ -648,7 +666,8 @@ uint32_t PoaBatch::run_large_pass() {
       unsigned long long sum[kSlots] = {0};
       unsigned long long longest = 0;
       for (size_t i = 0; i < n; ++i) {
-        for (size_t k = 0; k < kSlots; ++k) sum[k] += t[i * kSlots + k];
+        for (size_t k = 0; k < kSlots - 1; ++k) sum[k] += t[i * kSlots + k];
+        sum[7] += poa_count_layers(t[i * kSlots + 7]);  // poa_pack_counts
         longest = std::max(longest, t[i * kSlots + 6]);
       }
       fprintf(stderr,
@@ -717,6 +736,7 @@ void PoaBatch::reset() {
   large_nodes_of_.clear();
   large_completed_ = 0;
   score_refused_ = 0;
+  lean_rows_ = true;
   windows_.clear();
   seqs_added_.clear();
   pending_orders_.clear();

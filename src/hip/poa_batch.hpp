@@ -64,6 +64,15 @@ class PoaBatch {
   // windows of the last generate() that ended with kPoaScoreRange
   uint32_t score_refused() const { return score_refused_; }
 
+  // Lean single-predecessor rows (poa_kernel.hip, dp_row_lean), on by default.
+  // Off, every row takes the general row; results are the same either way.
+  // The rows run lean only where poa_lean_rows_fit holds for the batch's
+  // scores, and RGA_POA_LEAN_ROWS=0 in the environment switches them off for
+  // every batch of the process. The setting is the caller's, not the batch's
+  // history: reset() puts it back on, so a pooled batch carries none over.
+  void set_lean_rows(bool on) { lean_rows_ = on; }
+  bool lean_rows() const { return lean_rows_; }
+
   // Runs the kernel and writes consensus into the windows; returns per-window
   // polish status (false = needs CPU fallback or <3-layer backbone copy).
   std::vector<bool> generate(bool trim);
@@ -104,6 +113,7 @@ class PoaBatch {
   uint32_t max_depth_;
   bool score_check_ = false;  // the checked kernels run, both passes
   uint32_t score_refused_ = 0;
+  bool lean_rows_ = true;
 
   // pinned host staging
   uint8_t* h_seq_ = nullptr;

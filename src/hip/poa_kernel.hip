@@ -1264,6 +1264,246 @@ __device__ __forceinline__ void dp_row(const WindowCtx c, SH& s, const LayerDp& 
   }
 }
 
+// ---------- the lean row ----------
+
+// Two int16 values in one register, the lower column in the low half: the
+// layout of a ring row, so a 16-byte ring load is four of them as it stands.
+using pk16 = short __attribute__((ext_vector_type(2)));
+using pku16 = unsigned short __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ pk16 pk_from(uint32_t w) { return __builtin_bit_cast(pk16, w); }
+__device__ __forceinline__ uint32_t pk_bits(pk16 v) { return __builtin_bit_cast(uint32_t, v); }
+__device__ __forceinline__ pk16 pk_splat(int32_t v) {
+  return pk16{static_cast<short>(v), static_cast<short>(v)};
+}
+__device__ __forceinline__ pk16 pk_max(pk16 a, pk16 b) { return __builtin_elementwise_max(a, b); }
+__device__ __forceinline__ pk16 pk_lo(pk16 a) { return __builtin_shufflevector(a, a, 0, 0); }
+__device__ __forceinline__ pk16 pk_hi(pk16 a) { return __builtin_shufflevector(a, a, 1, 1); }
+// the pair one column further on: (a's high half, b's low half)
+__device__ __forceinline__ pk16 pk_next(pk16 a, pk16 b) {
+  return pk_from(__builtin_amdgcn_alignbit(pk_bits(b), pk_bits(a), 16));
+}
+// per half: 1 where the halves of a and b differ, else 0. The instruction is
+// written out: as an elementwise min of the xor with 1 the compiler turns it
+// back into two 16-bit compares, two selects and a byte permute per pair.
+__device__ __forceinline__ uint32_t pk_differ(pk16 a, pk16 b) {
+  const uint32_t x = pk_bits(a) ^ pk_bits(b);
+  uint32_t r;
+  asm("v_pk_min_u16 %0, %1, %2" : "=v"(r) : "v"(x), "s"(0x00010001u));
+  return r;
+}
+
+// poa_code for a letter in a scalar register, without the switch's branches:
+// bits 1..2 of 'A', 'C', 'T', 'G' are 0, 1, 2, 3.
+__device__ __forceinline__ int32_t poa_code_uniform(uint32_t letter) {
+  const uint32_t idx = letter - 'A';
+  // 'A', 'C', 'G', 'T' are 0, 2, 6 and 19 letters behind 'A'
+  if (idx > 19u || ((0x80045u >> idx) & 1u) == 0) {
+    return -1;
+  }
+  const uint32_t t = (letter >> 1) & 3u;  // A 0, C 1, G 3, T 2
+  return static_cast<int32_t>(t ^ (t >> 1));
+}
+static_assert((('A' >> 1) & 3) == 0 && (('C' >> 1) & 3) == 1 && (('G' >> 1) & 3) == 3 &&
+              (('T' >> 1) & 3) == 2 && 'C' - 'A' == 2 && 'G' - 'A' == 6 && 'T' - 'A' == 19);
+
+// dp_row for the common row, on packed int16 pairs. The kernel's row loop
+// sends a row here when (all wave-uniform, tested on scalar registers)
+//   - the kernel is an 8-wide, unchecked one of the regular class,
+//   - the launch's score parameters pass poa_lean_rows_fit and the batch has
+//     the lean row on (PoaDeviceArena::lean_rows),
+//   - the layer is unbanded and at most kPoaLeanMaxLen = 64 * 8 columns long,
+//     so the row is one pass,
+//   - the node has exactly one in-edge, usable under the layer's rank window
+//     (pred0 > rlo when d.sub), whose source row is in the LDS ring,
+//   - the node's letter is A, C, G or T (`code`).
+// Every other row goes through dp_row. The row leaves behind exactly what
+// dp_row leaves: ring_row and Hrow in columns 0..len, the move bytes, the
+// running alignment end. Rows of both kinds alternate freely.
+//
+// What dp_row does and this row does not, and why the result does not need it:
+//   - no okmask. The predecessor row is complete in columns 0..len (an
+//     unbanded row writes them all, the explicit tail column included), so
+//     the mask would only turn columns past len into minus infinity. Those
+//     hold whatever the LDS held. Column j reads the predecessor's columns
+//     j - 1 and j and, through the scan, this row's columns below j: junk
+//     flows only from a column past len to columns past it. It never reaches
+//     the value at column len (last_col_val), and the move bytes of columns
+//     past len are cleared before the store, as in dp_row. Score columns past
+//     len are stored as junk where dp_row stores floor values; every reader,
+//     dp_row's okmask or this argument, ignores them.
+//   - no edge loop, no candidate initial value, no edge index: the one edge
+//     is in-edge 0, and a move byte's edge field is 0.
+//   - column 0 is the low half of lane 0's ring load plus the gap score:
+//     no read of its own, and no global read that the ring read would have
+//     to share a register (and a vmcnt wait) with.
+//   - the match bits are one byte per lane: cbase is a multiple of 8, so a
+//     lane's eight bits never straddle a word of Shared::match.
+//
+// Range (poa_types.hpp, poa_lean_rows_fit). No value of a valid column leaves
+// int16: stored scores are within 28000 of zero, candidates add one
+// parameter, the u-space values at most 512 * |g|. So plain packed adds
+// serve, and a wrap can happen only in a junk column, which feeds junk
+// columns alone; there is no saturating add in the row because none could
+// change a valid column. The move-byte tests are comparisons for equality
+// (max == candidate, h == v), which cannot overflow. The wave scan runs on the
+// lane totals sign-extended to 32 bits, with dp_row's scan and its identity.
+template <uint32_t MAXW, class SH>
+__device__ __forceinline__ void dp_row_lean(const WindowCtx c, SH& s, const LayerDp& d,
+                                            uint32_t r, uint32_t rd_hi, int32_t code, int lane_id,
+                                            int32_t& best_score, uint32_t& best_row) {
+  constexpr uint32_t WB = 8;
+  // What the row derives from the lane id (addresses, the j * g pairs) does
+  // not change from row to row, so the compiler would keep it in VGPRs across
+  // the whole row loop, dp_row's rows included, which have none to spare (it
+  // spilled them). Recomputing costs a handful of instructions per row: hide
+  // the lane id from loop-invariant code motion, as the kernel does for its
+  // graph phases.
+  int lane = lane_id;
+  asm volatile("" : "+v"(lane));
+  static_assert(kLanes * WB + 1 <= MAXW, "column cbase + 8 of lane 63 is inside the ring row");
+  static_assert(kLanes * WB == kPoaLeanMaxLen);
+  static_assert(kLanes * WB < kMaxW, "a lane's eight move bytes never reach the column-0 slot");
+  const uint32_t len = d.len;
+  const uint32_t pred0 = rd_hi & 0xffffu;
+  const bool is_end = ((rd_hi >> 16) & kRdEnd) != 0;
+  const bool store_row = ((rd_hi >> 16) & kRdStore) != 0;
+  int16_t* Hrow = c.matrix + static_cast<size_t>(r + 1) * kMaxW;
+  uint8_t* Mrow = c.moves + static_cast<size_t>(r + 1) * kMaxW;
+  int16_t* ring_row = s.u.dp.ring[(r + 1) % kRing];
+  const int16_t* pred_row = s.u.dp.ring[pred0 % kRing];
+
+  const uint32_t cbase = static_cast<uint32_t>(lane) * WB;  // own cols: cbase+1..cbase+8
+  const int4 pvec = *reinterpret_cast<const int4*>(&pred_row[cbase]);
+  const uint32_t pv8 = static_cast<uint16_t>(pred_row[cbase + WB]);
+  const uint32_t mb = reinterpret_cast<const uint8_t*>(s.u.dp.match[code])[lane];
+
+  // column 0: a vertical move through the one edge
+  const int32_t h0 =
+      static_cast<int16_t>(__builtin_amdgcn_readfirstlane(pvec.x) & 0xffff) + c.g;
+
+  // P[q]: predecessor columns cbase + 2q, + 2q + 1, the diagonal neighbours
+  // of own columns 2q and 2q + 1; N[q]: one column on, the vertical ones
+  const pk16 P[4] = {pk_from(pvec.x), pk_from(pvec.y), pk_from(pvec.z), pk_from(pvec.w)};
+  const pk16 N[4] = {pk_next(P[0], P[1]), pk_next(P[1], P[2]), pk_next(P[2], P[3]),
+                     pk_next(P[3], pk_from(pv8))};
+  const pk16 gg = pk_splat(c.g);
+  const pku16 xx = __builtin_bit_cast(pku16, pk_splat(c.x));
+  const pku16 mx = __builtin_bit_cast(pku16, pk_splat(c.m - c.x));
+  // match bit i of the lane at bits i and i + 15: shifted right by 2q, bits 0
+  // and 16 are those of own columns 2q and 2q + 1
+  const uint32_t spread = mb * 0x8001u;
+  // j * g of own columns 2q, 2q + 1 (j = cbase + 1 + w, at most 512 * |g|)
+  const int32_t jg0 = static_cast<int32_t>(cbase + 1) * c.g;
+  const pk16 jg01 = pk16{static_cast<short>(jg0), static_cast<short>(jg0 + c.g)};
+  pk16 V[4], JG[4];
+  uint32_t up[4];  // per half: 1 where the vertical candidate wins (diagonal on a tie)
+#pragma unroll
+  for (uint32_t q = 0; q < 4; ++q) {
+    const pku16 bit = __builtin_bit_cast(pku16, (spread >> (2 * q)) & 0x00010001u);
+    const pk16 subst = __builtin_bit_cast(pk16, static_cast<pku16>(bit * mx + xx));
+    const pk16 bd = P[q] + subst;
+    const pk16 bu = N[q] + gg;
+    V[q] = pk_max(bd, bu);
+    up[q] = pk_differ(V[q], bd);
+    JG[q] = jg01 + pk_splat(static_cast<int32_t>(2 * q) * c.g);
+  }
+
+  // inclusive u-space scan over own columns: within a pair, then along the
+  // pairs through the high half of the one before
+  pk16 R[4];
+#pragma unroll
+  for (uint32_t q = 0; q < 4; ++q) {
+    const pk16 u = V[q] - JG[q];
+    R[q] = pk_max(u, pk_lo(u));
+    if (q != 0) {
+      R[q] = pk_max(R[q], pk_hi(R[q - 1]));
+    }
+  }
+  const int32_t run = static_cast<int32_t>(pk_bits(R[3])) >> 16;
+  const int32_t incl = wave_scan_max(run);
+  int32_t excl = __builtin_amdgcn_update_dpp(kNegInf, incl, 0x138, 0xf, 0xf, false);  // wave_shr:1
+  excl = max(excl, h0);  // column 0 in u-space is h0 itself; real from here on
+  const pk16 ex = pk_from(__builtin_amdgcn_perm(0u, static_cast<uint32_t>(excl), 0x01000100u));
+
+  // scores, clamped for the store; a left move where the scan strictly wins
+  const pk16 floor2 = pk_splat(kPoaScoreFloor);
+  pk16 H[4], HC[4];
+  uint32_t mv[4];  // per half: the move byte
+#pragma unroll
+  for (uint32_t q = 0; q < 4; ++q) {
+    H[q] = pk_max(R[q], ex) + JG[q];
+    HC[q] = pk_max(H[q], floor2);
+    const uint32_t left = pk_differ(H[q], V[q]);
+    static_assert(kMvDiag == 0 && kMvUp == 1 && kMvLeft == 2);
+    mv[q] = __builtin_bit_cast(
+        uint32_t, __builtin_elementwise_max(__builtin_bit_cast(pku16, up[q]),
+                                            __builtin_bit_cast(pku16, left + left)));
+  }
+  uint64_t mvpack =
+      static_cast<uint64_t>(__builtin_amdgcn_perm(mv[1], mv[0], 0x06040200u)) |
+      (static_cast<uint64_t>(__builtin_amdgcn_perm(mv[3], mv[2], 0x06040200u)) << 32);
+
+  // the shifted 16-byte row store of dp_row: column cbase is the lane
+  // below's last value, h0 for lane 0
+  const uint32_t shifted = static_cast<uint32_t>(__builtin_amdgcn_update_dpp(
+      static_cast<int32_t>(static_cast<uint32_t>(h0) << 16), static_cast<int32_t>(pk_bits(HC[3])),
+      0x138, 0xf, 0xf, false));
+  if (cbase < len) {
+    int4 vec;
+    vec.x = static_cast<int32_t>(__builtin_amdgcn_alignbit(pk_bits(HC[0]), shifted, 16));
+    vec.y = static_cast<int32_t>(pk_bits(pk_next(HC[0], HC[1])));
+    vec.z = static_cast<int32_t>(pk_bits(pk_next(HC[1], HC[2])));
+    vec.w = static_cast<int32_t>(pk_bits(pk_next(HC[2], HC[3])));
+    *reinterpret_cast<int4*>(&ring_row[cbase]) = vec;
+    if (store_row) {
+      *reinterpret_cast<int4*>(Hrow + cbase) = vec;
+    }
+    const uint32_t nown = min(WB, len - cbase);
+    if (nown < WB) {
+      mvpack &= (1ull << (8 * nown)) - 1;  // columns past the row end carry byte 0
+    }
+    *reinterpret_cast<uint64_t*>(Mrow + cbase) = mvpack;
+  }
+  if (lane == 0) {
+    Mrow[kMaxW - 1] = kMvUp;  // column 0, edge 0
+  }
+  // a row length on a lane boundary: the lane that would store column len in
+  // its shifted slot has cbase == len (dp_row has the story)
+  if ((len & (WB - 1)) == 0) {
+    const uint32_t t16 =
+        static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int32_t>(pk_bits(HC[3])),
+                                                        static_cast<int>(len / WB) - 1)) >> 16;
+    if (lane == 0) {
+      ring_row[len] = static_cast<int16_t>(t16);
+      if (store_row) {
+        Hrow[len] = static_cast<int16_t>(t16);
+      }
+    }
+  }
+
+  wave_lds_sync();
+
+  // end-node max, as in dp_row; the unclamped score at column len is taken
+  // from the registers only on the rows that can end an alignment
+  if (is_end || (d.sub && r == d.rhi)) {
+    const int owner = static_cast<int>((len - 1) / WB);
+    const uint32_t w = (len - 1) & (WB - 1);
+    const uint32_t s0 = __builtin_amdgcn_readlane(static_cast<int32_t>(pk_bits(H[0])), owner);
+    const uint32_t s1 = __builtin_amdgcn_readlane(static_cast<int32_t>(pk_bits(H[1])), owner);
+    const uint32_t s2 = __builtin_amdgcn_readlane(static_cast<int32_t>(pk_bits(H[2])), owner);
+    const uint32_t s3 = __builtin_amdgcn_readlane(static_cast<int32_t>(pk_bits(H[3])), owner);
+    const uint32_t pair = w < 2 ? s0 : w < 4 ? s1 : w < 6 ? s2 : s3;
+    const int32_t last_col_val =
+        (w & 1) != 0 ? static_cast<int32_t>(pair) >> 16
+                     : static_cast<int32_t>(static_cast<int16_t>(pair & 0xffffu));
+    if (last_col_val > best_score) {
+      best_score = last_col_val;
+      best_row = r + 1;
+    }
+  }
+}
+
 // ---------- traceback ----------
 
 // rounds of the traceback read this many moves of the predicted path at once
@@ -1456,6 +1696,9 @@ __global__ void poa_window_kernel(PoaDeviceArena a, uint32_t window_base,
   const unsigned long long t_start = tick;
   unsigned long long t_dp = 0, t_tb = 0, t_add = 0, t_topo = 0, t_rd = 0, t_cons = 0;
   unsigned long long layers_done = 0;
+  uint32_t rows_done = 0, rows_lean = 0;  // TIMED: DP rows, and those of the lean row
+  // the instantiations that have the lean row at all
+  constexpr bool kLeanKernel = WB == 8 && !kLarge && !CHECKED;
   auto lap = [&]() -> unsigned long long {
     if (!TIMED) {
       return 0;
@@ -1512,6 +1755,9 @@ __global__ void poa_window_kernel(PoaDeviceArena a, uint32_t window_base,
                                                  (d.rhi - d.rlo + 1))
                          : 0;
 
+    // lean rows (dp_row_lean): what the layer has to be; the rest is per row
+    const bool lean_layer = kLeanKernel && a.lean_rows != 0 && !d.banded && len <= kPoaLeanMaxLen;
+
     int32_t best_score = kNegInf;
     uint32_t best_row = 0;
     uint32_t score_low = 0;  // CHECKED: a row of this layer was refused
@@ -1529,6 +1775,30 @@ __global__ void poa_window_kernel(PoaDeviceArena a, uint32_t window_base,
       wave_lds_sync();
       const uint32_t rlim = min(d.rhi + 1, rblk + kLanes);
       for (uint32_t r = max(rblk, d.rlo); r < rlim; ++r) {
+        if constexpr (kLeanKernel) {
+          // the row's eligibility for the lean row, on scalar registers (the
+          // descriptor is wave-uniform but arrives in vector registers)
+          if (lean_layer) {
+            const uint64_t rdv = s.u.dp.rd_block[r - rblk];
+            const uint32_t rd_lo = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(rdv));
+            const uint32_t rd_hi =
+                __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(rdv >> 32));
+            const uint32_t pred0 = rd_hi & 0xffffu;
+            const int32_t code = poa_code_uniform(rd_lo & 0xffu);
+            if (((rd_lo >> 8) & 0xffu) == 1 && code >= 0 && r + 1 - pred0 < kRing &&
+                (!d.sub || pred0 > d.rlo)) {
+              dp_row_lean<MAXW>(c, s, d, r, rd_hi, code, lane, best_score, best_row);
+              if (TIMED) {
+                ++rows_lean;
+                ++rows_done;
+              }
+              continue;
+            }
+          }
+        }
+        if (TIMED) {
+          ++rows_done;
+        }
         dp_row<CHECKED, WB, MAXW>(c, s, d, r, s.u.dp.rd_block[r - rblk],
                                   s.u.dp.rd2_block[r - rblk], lane, best_score, best_row,
                                   score_low);
@@ -1617,7 +1887,7 @@ __global__ void poa_window_kernel(PoaDeviceArena a, uint32_t window_base,
       timing[4] = t_rd;
       timing[5] = t_cons;
       timing[6] = wall_clock64() - t_start;
-      timing[7] = layers_done;
+      timing[7] = poa_pack_counts(layers_done, rows_lean, rows_done);
     }
   }
 }

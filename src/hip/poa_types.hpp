@@ -99,6 +99,32 @@ static_assert(poa_score_check_static(27, -20, -13, 1024) &&
               !poa_score_check_static(3, -5, 0, 1024));
 static_assert(!poa_score_row_refused(-14000, 500, -28) && poa_score_row_refused(-14500, 500, -29));
 
+// ---- lean single-predecessor rows ----
+// The 8-wide unchecked kernels of the regular class compute a row with exactly
+// one in-edge, whose source row is in the LDS ring, on packed int16 pairs
+// (poa_kernel.hip, dp_row_lean; docs/DESIGN.md, "Lean rows"). A lean row is a
+// single pass, so its columns stop at kPoaLeanMaxLen. What it holds in 16 bits:
+//   stored scores          [kPoaScoreFloor, -kPoaScoreFloor]   (floor clamp,
+//                          constructor guard)
+//   candidates, v, h       one score parameter more on either side
+//   u-space values         v - j * g, j <= kPoaLeanMaxLen
+// The row has no "no cell" value of its own: its one predecessor row is
+// complete, and the wave scan, which has one, runs on 32 bits. So the
+// condition is that the largest u-space value fits, with a negative gap, which
+// is what the direction of the u-space argument (u >= v, junk columns only
+// feed higher columns) is written for. Every parameter set that passes the
+// worst-case guard with a negative gap passes it (28000 + 9 + 512 * 9 =
+// 32617); a batch that fails it runs every row through dp_row.
+inline constexpr uint32_t kPoaLeanMaxLen = 512;
+constexpr bool poa_lean_rows_fit(int32_t m, int32_t x, int32_t g) {
+  return g < 0 && -kPoaScoreFloor + poa_max(poa_abs(m), poa_max(poa_abs(x), poa_abs(g))) +
+                          static_cast<int32_t>(kPoaLeanMaxLen) * poa_abs(g) <=
+                      32767;
+}
+static_assert(poa_lean_rows_fit(3, -5, -4) && poa_lean_rows_fit(5, -4, -8) &&
+              poa_lean_rows_fit(3, -8, -4) && poa_lean_rows_fit(9, -9, -9) &&
+              !poa_lean_rows_fit(3, -5, 0) && !poa_lean_rows_fit(3, -5, -10));
+
 // ---- kernel variants ----
 // The kernel is instantiated once per row of kPoaVariants (times timed /
 // untimed). The enum's numeric order is the order a batch's windows are
@@ -247,6 +273,19 @@ constexpr void for_each_poa_slab(PoaSlabs& s, F&& f) {
 }
 
 constexpr size_t kPoaTimingSlots = 8;
+// Timing slot 7 carries three counts, so that the slab layout stays what it
+// was: layers processed in bits 0..15, DP rows taken by the lean row in bits
+// 16..39 and DP rows in all in bits 40..63 (a window has at most 200 layers of
+// at most 4095 rows).
+constexpr unsigned long long poa_pack_counts(unsigned long long layers, unsigned long long lean,
+                                             unsigned long long rows) {
+  return layers | (lean << 16) | (rows << 40);
+}
+constexpr unsigned long long poa_count_layers(unsigned long long w) { return w & 0xffffu; }
+constexpr unsigned long long poa_count_lean_rows(unsigned long long w) {
+  return (w >> 16) & 0xffffffu;
+}
+constexpr unsigned long long poa_count_rows(unsigned long long w) { return w >> 40; }
 
 // device scratch bytes one window needs (unrounded; sizes the batch)
 template <bool LARGE = false>
@@ -295,6 +334,10 @@ struct PoaDeviceArena {
                             // the device unless PoaBatch::read_graph asks
 
   int8_t match, mismatch, gap;
+  // 1: eligible rows take the lean row (poa_lean_rows_fit holds and the batch
+  // has not switched it off). In the padding behind gap: the struct's size and
+  // the other members' offsets are what they were.
+  uint8_t lean_rows;
   uint32_t band_width;  // 0 = full-width DP; else static band (reference -b:
                         // BatchConfig band 256, src/cuda/cudabatch.cpp:56-59)
 };

@@ -39,12 +39,13 @@ std::vector<std::pair<std::string, bool>> poa_windows_gpu(
     const std::vector<std::vector<std::tuple<std::string, std::string, uint32_t, uint32_t>>>&
         window_layers,
     int8_t match, int8_t mismatch, int8_t gap, bool banded, bool trim, bool tgs,
-    bool large_graphs, bool score_check);
+    bool large_graphs, bool score_check, bool lean_rows);
 std::vector<std::tuple<int32_t, std::vector<uint16_t>, std::vector<std::vector<uint16_t>>>>
 poa_window_graph_gpu(
     const std::vector<std::vector<std::tuple<std::string, std::string, uint32_t, uint32_t>>>&
         window_layers,
-    int8_t match, int8_t mismatch, int8_t gap, bool banded, bool large_graphs, bool score_check);
+    int8_t match, int8_t mismatch, int8_t gap, bool banded, bool large_graphs, bool score_check,
+    bool lean_rows);
 }
 
 namespace py = pybind11;
@@ -387,30 +388,33 @@ PYBIND11_MODULE(_racon, m) {
   m.def("poa_windows_gpu", [](const std::vector<std::vector<
                                   std::tuple<std::string, std::string, uint32_t, uint32_t>>>& w,
                               int8_t match, int8_t mismatch, int8_t gap, bool banded,
-                              bool trim, bool tgs, bool large_graphs, bool score_check) {
+                              bool trim, bool tgs, bool large_graphs, bool score_check,
+                              bool lean_rows) {
     py::gil_scoped_release release;
     return rga::hip::poa_windows_gpu(w, match, mismatch, gap, banded, trim, tgs, large_graphs,
-                                     score_check);
+                                     score_check, lean_rows);
   }, py::arg("windows"), py::arg("match") = 3, py::arg("mismatch") = -5,
      py::arg("gap") = -4, py::arg("banded") = false, py::arg("trim") = true,
-     py::arg("tgs") = true, py::arg("large_graphs") = false, py::arg("score_check") = false);
+     py::arg("tgs") = true, py::arg("large_graphs") = false, py::arg("score_check") = false,
+     py::arg("lean_rows") = true);
   m.def("poa_window_graph_gpu",
         [](const std::vector<
                std::vector<std::tuple<std::string, std::string, uint32_t, uint32_t>>>& w,
            int8_t match, int8_t mismatch, int8_t gap, bool banded, bool large_graphs,
-           bool score_check) {
+           bool score_check, bool lean_rows) {
           py::gil_scoped_release release;
           return rga::hip::poa_window_graph_gpu(w, match, mismatch, gap, banded, large_graphs,
-                                                score_check);
+                                                score_check, lean_rows);
         },
         py::arg("windows"), py::arg("match") = 3, py::arg("mismatch") = -5, py::arg("gap") = -4,
         py::arg("banded") = false, py::arg("large_graphs") = false,
-        py::arg("score_check") = false,
+        py::arg("score_check") = false, py::arg("lean_rows") = true,
         "Test entry: the windows through the GPU POA kernel in one batch, then per window "
         "(status, rank per node, out-edge targets per node) read back from its slab; the "
         "lists are empty unless status is 0. large_graphs: with the large-graph pass, whose "
         "windows are read back from their large slabs. score_check: with the per-window "
-        "score check; a refused window has status 7.");
+        "score check; a refused window has status 7. lean_rows=False: every DP row through the "
+        "general row (poa_windows_gpu takes the same switch).");
   m.def("poa_consensus", &poa_consensus, py::arg("sequences"),
         py::arg("qualities") = std::vector<std::string>(), py::arg("match") = 5,
         py::arg("mismatch") = -4, py::arg("gap") = -8);
